@@ -7,6 +7,13 @@ C2-sized channel (2^26 cf32 @ 10 Msps, its own tuning offset; BASELINE.json
 configs[1]). Channels are independent: no collective on the data path
 ("scaling": "weak"); the only collectives are the timing barrier / max.
 
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step` and the event-timed roofline of those K steps).
+--dump-outputs DIR also writes the last timed step's output to DIR/out.npy (the
+inputs are seeded, so two builds' files compare value for value). Everything that
+takes runs of its own (per-launch spread, measured read ceiling, C5F's kernels one
+by one, host_fed, cpu_baseline and its parity figure) is behind --full.
+
 The roofline object prices the one kernel the chain runs (k_wbfm_seg) with
 HIP events on the stream it is launched on (one pair around the K launches, so
 inter-launch gaps count against it): algorithmic bytes per launch
@@ -17,7 +24,7 @@ single-threaded) timed on this host on a bounded prefix of the same input; the
 multi-channel configs time the oracle on min(channels, 16) host threads, one
 channel per thread, on a bounded prefix of that many channels.
 
-At N = 1 the C2 line also carries "host_fed" (SURVEY §8d's H2D-inclusive figure): the
+At N = 1 the C2 line of a --full run also carries "host_fed" (SURVEY §8d's H2D-inclusive figure): the
 same chain driven from host memory through orion_block_process, pinned and pageable,
 beside the box's raw pinned H2D rate. It is never `value`.
 
@@ -444,6 +451,23 @@ def host_fed(x_dev, passes=3):
                     "per sample"}
 
 
+DUMP_MAX_VALUES = 1 << 23  # float32 values per dumped array (32 MiB: the whole C2 audio)
+
+
+def dump_output(out, directory, name):
+    """--dump-outputs: the timed path's output buffer as DIR/<name>.npy in float32 (a
+    complex output as (re, im) pairs in a last axis of 2). An output of more than
+    DUMP_MAX_VALUES values is written as that many of them, taken at seeded positions of
+    the flattened buffer (ascending; the same positions on every run), so the files of two
+    builds compare value for value."""
+    v = torch.view_as_real(out) if out.is_complex() else out
+    if v.numel() > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(0x0D0C).integers(0, v.numel(), DUMP_MAX_VALUES))
+        v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), v.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -467,7 +491,15 @@ def main():
                     help="comma list: the device of each local rank (default: local rank i on device i)")
     ap.add_argument("--check-shards", action="store_true",
                     help="C2 stream shards: gather the ranks' audio and compare with one call over the stream")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the per-launch spread, the "
+                         "measured read ceiling, C5F's kernels one by one, the host-fed C2 figure and the CPU "
+                         "baseline with its parity figure (--no-cpu / --no-h2d drop the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -528,6 +560,8 @@ def main():
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, dev)
     kern_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:  # before anything else runs the (stateful) block into `out` again
+        dump_output(out, args.dump_outputs, "out" if world == 1 else f"out_rank{rank}")
 
     total = samples * world * args.steps
     value = total / elapsed / 1e6
@@ -548,7 +582,9 @@ def main():
                      "kernel_ms": round(kern_ms, 4), "bytes_per_sample": bps},
         "cpu_baseline": None,
     }
-    if args.config == "c5f":
+    if args.config == "c5f" and not args.full:
+        line["roofline"]["kernel_ms_covers"] = "both launches of a step (--full times the FIR alone)"
+    if args.config == "c5f" and args.full:
         # the dominant kernel alone (the 127-tap FIR, FP32-bound: 508 flop per sample), one
         # event pair around each FIR launch after the timed region; the SSB scan beside it
         mid = torch.empty_like(x)
@@ -577,35 +613,36 @@ def main():
                                 hbm_frac=round(achieved / HBM_PEAK_GBS, 4))
     # per-launch spread (after the timed region): one event pair per launch,
     # so the clock's step-down across back-to-back launches is visible beside the average
-    pairs = []
-    for _ in range(max(args.steps, 10)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        step()
-        e1.record(stream)
-        pairs.append((e0, e1))
-    torch.cuda.synchronize(dev)
-    per = sorted(e0.elapsed_time(e1) for e0, e1 in pairs)
-    line["roofline"]["per_launch_ms"] = {"min": round(per[0], 4), "median": round(per[len(per) // 2], 4),
-                                         "max": round(per[-1], 4), "launches": len(per)}
-    # on-box read ceiling (after the timed region): the library's streaming-read probe
-    # over this rank's input, 10 launches between events. Diagnostic
-    # only: a probe that cannot run (input below one tile per wave) leaves it null.
-    try:
-        nb = orion_sdr.diag_stream_read(x, stream.cuda_stream) if args.config != "c1" else 0
-        if nb > 0:
-            p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            p0.record(stream)
-            for _ in range(10):
-                orion_sdr.diag_stream_read(x, stream.cuda_stream)
-            p1.record(stream)
-            torch.cuda.synchronize(dev)
-            peak_meas = nb / (p0.elapsed_time(p1) / 10 * 1e-3) / 1e9
-            line["roofline"]["peak_measured"] = round(peak_meas, 1)
-            line["roofline"]["frac_measured"] = round(achieved / peak_meas, 4)
-    except Exception as e:  # noqa: BLE001  (the bench line must still print)
-        line["roofline"]["peak_measured"] = None
-        line["roofline"]["probe_error"] = str(e)[:120]
+    if args.full:
+        pairs = []
+        for _ in range(max(args.steps, 10)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            step()
+            e1.record(stream)
+            pairs.append((e0, e1))
+        torch.cuda.synchronize(dev)
+        per = sorted(e0.elapsed_time(e1) for e0, e1 in pairs)
+        line["roofline"]["per_launch_ms"] = {"min": round(per[0], 4), "median": round(per[len(per) // 2], 4),
+                                             "max": round(per[-1], 4), "launches": len(per)}
+        # on-box read ceiling (after the timed region): the library's streaming-read probe
+        # over this rank's input, 10 launches between events. Diagnostic
+        # only: a probe that cannot run (input below one tile per wave) leaves it null.
+        try:
+            nb = orion_sdr.diag_stream_read(x, stream.cuda_stream) if args.config != "c1" else 0
+            if nb > 0:
+                p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                p0.record(stream)
+                for _ in range(10):
+                    orion_sdr.diag_stream_read(x, stream.cuda_stream)
+                p1.record(stream)
+                torch.cuda.synchronize(dev)
+                peak_meas = nb / (p0.elapsed_time(p1) / 10 * 1e-3) / 1e9
+                line["roofline"]["peak_measured"] = round(peak_meas, 1)
+                line["roofline"]["frac_measured"] = round(achieved / peak_meas, 4)
+        except Exception as e:  # noqa: BLE001  (the bench line must still print)
+            line["roofline"]["peak_measured"] = None
+            line["roofline"]["probe_error"] = str(e)[:120]
     # PMC traffic is collected in separate rocprofv3 --pmc passes (tools/traffic.py), never
     # inside this run: the figure is the committed file's, and the line names it
     traffic_file = os.path.join(ROOT, "profiles", f"traffic_{args.config}.json")
@@ -617,12 +654,13 @@ def main():
                                                  f"WRITE_SIZE, separate passes; not measured in this run)"
     if args.check_shards:
         line["shard_check"] = check_shards(x, desc, dist, world, rank, dev)
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_h2d:
+    solo = args.full and rank == 0 and world == 1  # the host-side figures: one process, --full only
+    if solo and args.config == "c2" and not args.no_h2d:
         try:
             line["host_fed"] = host_fed(x)
         except Exception as e:  # noqa: BLE001  (the bench line must still print)
             line["host_fed"] = {"error": str(e)[:160]}
-    if rank == 0 and world == 1 and not args.no_cpu and args.config in ("c1", "c2"):
+    if solo and not args.no_cpu and args.config in ("c1", "c2"):
         res = cpu_baseline(x, args.config, args.cpu_seconds, args.cpu_max_samples)
         if res:
             cb, xh, ref = res
@@ -632,7 +670,7 @@ def main():
             den = float(np.sqrt(np.mean(np.abs(ref.astype(np.complex128)) ** 2)))
             cb["gpu_vs_cpu_nrmse"] = float(np.sqrt(np.mean(np.abs(got.astype(np.complex128) - ref) ** 2)) / den)
             line["cpu_baseline"] = cb
-    elif rank == 0 and world == 1 and not args.no_cpu:
+    elif solo and not args.no_cpu:
         f_offs = [f for f, _ in channel_plan("c4", 0, 1)] if args.config == "c4" else None
         line["cpu_baseline"] = cpu_baseline_channels(x, args.config, min(args.cpu_seconds, 10.0), f_offs)
     if rank == 0:
