@@ -255,7 +255,10 @@ int orion_wbfm_chain_configure(orion_block* b, int path, int max_segments);
  * index of the next input sample, i.e. the NCO phase origin (rotator.rs:44-62
  * advances the phase once per sample from index 0). A shard of one stream is
  * processed by a fresh handle sought to its halo start, fed the halo and then
- * the shard (orion_sdr.stream_shard). ORION_E_TYPE if b is not a WBFM chain. */
+ * the shard (orion_sdr.stream_shard). A seek in the middle of a stream moves only the
+ * NCO phase: the decimator, discriminator, IIR and FIR state carry on, on every path.
+ * orion_block_reset on a chain returns to the last seek origin, not to index 0.
+ * ORION_E_TYPE if b is not a WBFM chain. */
 int orion_wbfm_chain_seek(orion_block* b, uint64_t index);
 
 /* ---- Block contract (core.rs:12-22) ------------------------------------ */
@@ -343,6 +346,76 @@ int orion_tx_lowpass_transition_fits(const orion_tx_lowpass* t, size_t n_fft, si
 float orion_tx_lowpass_stopband_edge_norm(const orion_tx_lowpass* t);                            /* :171-173 */
 int orion_tx_lowpass_fits_guard(const orion_tx_lowpass* t, size_t cp_len, size_t roll_off, size_t backoff); /* :179-182 */
 orion_block* orion_tx_lowpass_filter(const orion_tx_lowpass* t);                                 /* :185-187 */
+
+/* ---- FT8 / FT4 frame sync (src/sync; docs/demodulate.md:297-336) ----------------
+ * The search half of the reference's digital side: a symbol-rate Goertzel waterfall, the
+ * Costas candidate search and max-log LLRs, batched over nch independent channels
+ * ([nch][n_per_ch] cf32, channel-major; nch = 1 is the reference's call). Every cell,
+ * score and LLR is computed in the reference's f32 operation order: energies, scores,
+ * candidate lists (ties included) and LLRs equal the reference's bit for bit on the same
+ * waterfall; the waterfall's ln() is the device's (within 2 ulp of libm's).
+ * A sync handle owns what calls reuse (step table, scratch waterfall, score map) and is
+ * not a Block: there is no streaming state. One call at a time per handle.
+ * Limits (ORION_E_ARG beyond them): nch <= 65535, num_syms <= 65535, num_tones <= 2^20,
+ * nch * num_syms * num_tones < 2^31, max_cand <= 65536. */
+typedef struct orion_sync orion_sync;
+typedef struct {
+  int32_t time_sym;  /* costas.rs:29-36 Candidate (freq_bin: usize there) */
+  uint32_t freq_bin;
+  float score;
+} orion_candidate;
+#define ORION_SYNC_LLR 174  /* codec/ldpc.rs N: LLRs per candidate */
+#define ORION_WF_LOG 0      /* ln(e + 1e-12), waterfall.rs:114 */
+#define ORION_WF_ENERGY 1   /* e itself (goertzel_energy, waterfall.rs:126-151): bit-exact with the reference */
+#define ORION_COSTAS_FT8 0  /* [3,1,4,0,6,5,2] at frame symbols 0, 36, 72 (ft8_sync.rs:44-45) */
+#define ORION_COSTAS_FT4 1  /* four 4-tone patterns at 1, 34, 67, 100 (ft4_sync.rs:44-47) */
+orion_sync* orion_sync_new(void);
+void orion_sync_free(orion_sync* h);
+/* Engine tuning (no reference counterpart): symbol rows per lane of the waterfall kernel,
+ * 1, 2, 4 or 8; 0 (default) picks per call. Results do not depend on it. */
+int orion_sync_set_rows_per_lane(orion_sync* h, int rows);
+/* compute_waterfall, waterfall.rs:73-119. mag: [nch][num_syms][num_tones] f32. A row
+ * that starts at or past the end of the buffer stays 0.0 (in both modes); a row the
+ * buffer ends inside uses the samples it has; time_offset is any sample offset. */
+int orion_waterfall_compute(orion_sync* h, const void* iq, float fs, float base_hz, float tone_spacing_hz,
+                            size_t samples_per_sym, size_t num_syms, size_t num_tones, size_t time_offset,
+                            size_t nch, size_t n_per_ch, int mode, float* mag);
+int orion_waterfall_compute_device(orion_sync* h, const void* iq, float fs, float base_hz, float tone_spacing_hz,
+                                   size_t samples_per_sym, size_t num_syms, size_t num_tones, size_t time_offset,
+                                   size_t nch, size_t n_per_ch, int mode, float* mag, void* stream);
+/* find_candidates, costas.rs:125-174 (ORION_COSTAS_FT8) / find_ft4_candidates,
+ * ft4_sync.rs:122-163 (ORION_COSTAS_FT4) on a device waterfall [nch][num_syms][num_tones]:
+ * time_sym in t_min ..= t_max. cand: [nch][max_cand] records, best first, in the
+ * reference's order among equal scores; count: [nch] (slots past it are zeroed; 0 when
+ * num_tones <= the frame's tones). max_cand == 0 is ORION_E_ARG (the reference indexes an
+ * empty heap, costas.rs:159). */
+int orion_costas_find_candidates_device(orion_sync* h, const float* wf, size_t nch, size_t num_syms,
+                                        size_t num_tones, int pattern, int t_min, int t_max, size_t max_cand,
+                                        orion_candidate* cand, uint32_t* count, void* stream);
+/* extract_ft8_llr + normalise_llr, ft8_sync.rs:170-246 (extract_ft4_llr, ft4_sync.rs:227-292)
+ * for the first count[ch] candidates of each channel, on a device waterfall.
+ * llr: [nch][max_cand][ORION_SYNC_LLR] f32 (unused slots zeroed). */
+int orion_sync_llr_device(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern,
+                          const orion_candidate* cand, const uint32_t* count, size_t max_cand, float* llr,
+                          void* stream);
+/* ft8_sync, ft8_sync.rs:90-159, and ft4_sync, ft4_sync.rs:65-117: waterfall -> search ->
+ * LLRs, with the reference's num_bins, wf_syms, wf_sample_start and sym_offset_adj
+ * (ft8_sync.rs:99-131). cand [nch][max_cand] (time_sym relative to the buffer, as the
+ * reference returns it), count [nch], llr [nch][max_cand][ORION_SYNC_LLR]. Host slices
+ * (uploaded, one device call, downloaded; synchronous) or device buffers on a stream. */
+int orion_ft8_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                   int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr);
+int orion_ft8_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                          float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand,
+                          uint32_t* count, float* llr, void* stream);
+int orion_ft4_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                   int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr);
+int orion_ft4_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                          float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand,
+                          uint32_t* count, float* llr, void* stream);
+/* The geometry orion_ft8_sync / orion_ft4_sync derive (ft8_sync.rs:99-131), host only:
+ * geom[5] = num_bins, wf_syms, wf_sample_start, sym_offset_adj, wf_t_max. */
+int orion_sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max, size_t geom[5]);
 
 #ifdef __cplusplus
 }

@@ -11,10 +11,16 @@
 #include "blocks.hpp"
 #include "osc.hpp"
 #include "scan_blocks.hpp"
+#include "sync_blocks.hpp"
 
 struct orion_block {
   std::unique_ptr<orion::Block> impl;
 };
+struct orion_sync {
+  orion::Sync impl;
+};
+static_assert(sizeof(orion_candidate) == sizeof(orion::SyncCandidate) && sizeof(orion_candidate) == 12,
+              "orion_candidate is the kernels' record");
 
 namespace {
 thread_local std::string g_err;
@@ -564,6 +570,122 @@ orion_block* orion_tx_lowpass_filter(const orion_tx_lowpass* t) {
 void orion_lp_cascade_design(float fs, float fc, float out5[5]) {
   const auto c = orion::lp_cascade_design(fs, fc);
   out5[0] = c.b0; out5[1] = c.b1; out5[2] = c.b2; out5[3] = c.a1; out5[4] = c.a2;
+}
+
+/* ---- FT8 / FT4 sync (sync_blocks.hpp) ---- */
+orion_sync* orion_sync_new(void) {
+  try {
+    return new orion_sync;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_sync_free(orion_sync* h) { delete h; }
+int orion_sync_set_rows_per_lane(orion_sync* h, int rows) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    h->impl.set_rows_per_lane(rows);
+    return ORION_OK;
+  });
+}
+int orion_waterfall_compute(orion_sync* h, const void* iq, float fs, float base_hz, float tone_spacing_hz,
+                            size_t samples_per_sym, size_t num_syms, size_t num_tones, size_t time_offset,
+                            size_t nch, size_t n_per_ch, int mode, float* mag) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || (!mag && num_syms && num_tones)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.waterfall_host(iq, fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones, time_offset, nch,
+                           n_per_ch, mode, mag);
+    return ORION_OK;
+  });
+}
+int orion_waterfall_compute_device(orion_sync* h, const void* iq, float fs, float base_hz, float tone_spacing_hz,
+                                   size_t samples_per_sym, size_t num_syms, size_t num_tones, size_t time_offset,
+                                   size_t nch, size_t n_per_ch, int mode, float* mag, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || (!mag && num_syms && num_tones)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.waterfall(iq, fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones, time_offset, nch,
+                      n_per_ch, mode, mag, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_costas_find_candidates_device(orion_sync* h, const float* wf, size_t nch, size_t num_syms,
+                                        size_t num_tones, int pattern, int t_min, int t_max, size_t max_cand,
+                                        orion_candidate* cand, uint32_t* count, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!wf && num_syms && num_tones) || !count || (!cand && max_cand)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.find_candidates(wf, nch, num_syms, num_tones, pattern, t_min, t_max, max_cand,
+                            reinterpret_cast<orion::SyncCandidate*>(cand), count, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_sync_llr_device(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern,
+                          const orion_candidate* cand, const uint32_t* count, size_t max_cand, float* llr,
+                          void* stream) {
+  if ((!wf && num_syms && num_tones) || !count || !cand || !llr) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::sync_llr(wf, nch, num_syms, num_tones, pattern, reinterpret_cast<const orion::SyncCandidate*>(cand), count,
+                    max_cand, llr, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+namespace {
+int sync_device(int pattern, orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr,
+                void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || (max_cand && (!cand || !llr))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.sync(pattern, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand,
+                 reinterpret_cast<orion::SyncCandidate*>(cand), count, llr, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int sync_host(int pattern, orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+              float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || (max_cand && (!cand || !llr))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.sync_host(pattern, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand,
+                      reinterpret_cast<orion::SyncCandidate*>(cand), count, llr);
+    return ORION_OK;
+  });
+}
+}  // namespace
+int orion_ft8_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                   int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr) {
+  return sync_host(ORION_COSTAS_FT8, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, cand, count, llr);
+}
+int orion_ft8_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                          float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand,
+                          uint32_t* count, float* llr, void* stream) {
+  return sync_device(ORION_COSTAS_FT8, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, cand, count,
+                     llr, stream);
+}
+int orion_ft4_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                   int t_min, int t_max, size_t max_cand, orion_candidate* cand, uint32_t* count, float* llr) {
+  return sync_host(ORION_COSTAS_FT4, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, cand, count, llr);
+}
+int orion_ft4_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                          float max_hz, int t_min, int t_max, size_t max_cand, orion_candidate* cand,
+                          uint32_t* count, float* llr, void* stream) {
+  return sync_device(ORION_COSTAS_FT4, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, cand, count,
+                     llr, stream);
+}
+int orion_sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max, size_t geom[5]) {
+  if (!geom) return fail(ORION_E_NULL, "null argument");
+  return guarded([&] {
+    const orion::SyncGeometry g = orion::sync_geometry(pattern, base_hz, max_hz, t_min, t_max);
+    geom[0] = g.num_bins;
+    geom[1] = g.wf_syms;
+    geom[2] = g.wf_sample_start;
+    geom[3] = static_cast<size_t>(g.sym_offset_adj);
+    geom[4] = static_cast<size_t>(g.wf_t_max);
+    return ORION_OK;
+  });
 }
 
 }  // extern "C"

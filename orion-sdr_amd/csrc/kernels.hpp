@@ -170,4 +170,37 @@ void launch_stream_read(const void* x, long long bytes, float* sink, hipStream_t
 // Residency tests: `workgroups` one-wave workgroups holding lds_bytes of LDS each for
 // `seconds` of wall clock (bounded; every wave exits).
 void launch_spin(int workgroups, int lds_bytes, double seconds, hipStream_t s);
+
+// ------------------------------------------------- FT8 / FT4 sync (k_sync.hip) --
+// Waterfall (sync/waterfall.rs:73-151): x [nch][n] cf32, steps [num_tones] cf32 (the
+// per-tone step phasors, host libm), out [nch][num_syms][num_tones] f32. mode 0:
+// ln(e + 1e-12); 1: the energy e. rows_per_lane: 1, 2, 4 or 8 symbol rows per lane.
+void launch_waterfall(const f2* x_dev, const f2* steps_dev, float* out_dev, int nch, long long n, int sps, int num_syms,
+                      int num_tones, long long time_offset, int mode, int rows_per_lane, hipStream_t s);
+// A Costas search pattern: nblk blocks of len tones, block b at frame symbol pos[b];
+// tones: the FSK tones of a frame (bins it spans).
+struct CostasPattern {
+  int nblk, len, tones;
+  int pos[4];
+  int tone[4][7];
+};
+struct SyncCandidate {  // include/orion_sdr_amd.h orion_candidate
+  int32_t time_sym;
+  uint32_t freq_bin;
+  float score;
+};
+constexpr int kSyncLlr = 174;  // codec/ldpc.rs N
+// Candidate search (sync/costas.rs:125-174, sync/ft4_sync.rs:122-163) over wf
+// [nch][num_syms][num_tones]: score_dev holds nch * (t_max - t_min + 1) * (num_tones -
+// pat.tones + 1) floats of scratch; cand_dev [nch][max_cand] (unused slots zeroed),
+// count_dev [nch]. max_cand >= 1.
+void launch_costas_search(const float* wf_dev, float* score_dev, int nch, int num_syms, int num_tones,
+                          const CostasPattern& pat, int t_min, int t_max, int max_cand, SyncCandidate* cand_dev,
+                          uint32_t* count_dev, hipStream_t s);
+// Normalised LLRs (sync/ft8_sync.rs:170-246, sync/ft4_sync.rs:227-292): llr_dev
+// [nch][max_cand][174] (slots past a channel's count zeroed). cand_out_dev (optional, may
+// be cand_dev): the records with time_sym - sym_adj.
+void launch_sync_llr(const float* wf_dev, int nch, int num_syms, int num_tones, bool ft4, const SyncCandidate* cand_dev,
+                     const uint32_t* count_dev, int max_cand, float* llr_dev, SyncCandidate* cand_out_dev, int sym_adj,
+                     hipStream_t s);
 }  // namespace orion

@@ -1,0 +1,185 @@
+// sync_blocks.cpp — host side of the FT8 / FT4 sync front end (sync_blocks.hpp).
+#include "sync_blocks.hpp"
+
+#include <cmath>
+#include <stdexcept>
+
+namespace orion {
+
+namespace {
+// modulate/ft8.rs:9-18, sync/ft8_sync.rs:44-45; modulate/ft4.rs:9-24, sync/ft4_sync.rs:44-47
+struct Mode {
+  float spacing;
+  int sps, tones, total;
+  CostasPattern pat;
+};
+const Mode kFt8 = {6.25f, 1920, 8, 79,
+                   {3, 7, 8, {0, 36, 72, 0}, {{3, 1, 4, 0, 6, 5, 2}, {3, 1, 4, 0, 6, 5, 2}, {3, 1, 4, 0, 6, 5, 2}, {}}}};
+const Mode kFt4 = {20.833334f, 576, 4, 105,
+                   {4, 4, 4, {1, 34, 67, 100}, {{0, 1, 3, 2}, {1, 0, 2, 3}, {2, 3, 1, 0}, {3, 2, 0, 1}}}};
+const Mode& mode_of(int pattern) {
+  if (pattern == kCostasFt8) return kFt8;
+  if (pattern == kCostasFt4) return kFt4;
+  throw std::invalid_argument("unknown Costas pattern (ORION_COSTAS_FT8 / ORION_COSTAS_FT4)");
+}
+// Grid limits of the kernels (k_sync.hip): symbol-row groups and channels ride grid
+// dimensions y / z, cell indices are 32-bit.
+constexpr size_t kMaxSyms = 65535, kMaxTones = 1u << 20, kMaxCh = 65535, kMaxCand = 1u << 16;
+void check_grid(size_t nch, size_t num_syms, size_t num_tones) {
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
+  if (num_syms > kMaxSyms || num_tones > kMaxTones) throw std::invalid_argument("sync: num_syms <= 65535, num_tones <= 2^20");
+  if (nch * num_syms * num_tones > 0x7fffffffull) throw std::invalid_argument("sync: waterfall above 2^31 - 1 cells");
+}
+}  // namespace
+
+std::vector<float> waterfall_steps(float fs, float base_hz, float tone_spacing_hz, size_t num_tones) {
+  constexpr float kTau = 6.28318530717958647692f;
+  std::vector<float> w(2 * num_tones);
+  for (size_t k = 0; k < num_tones; ++k) {
+    const float f = base_hz + static_cast<float>(k) * tone_spacing_hz;
+    const float phi = -kTau * f / fs;
+    w[2 * k] = std::cos(phi);
+    w[2 * k + 1] = std::sin(phi);
+  }
+  return w;
+}
+
+SyncGeometry sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max) {
+  const Mode& m = mode_of(pattern);
+  const float d = max_hz - base_hz;
+  const float freq_range = d > 0.0f ? d : 0.0f;  // f32::max(0.0): a NaN gives 0
+  const float bins = std::ceil(freq_range / m.spacing);
+  if (!(bins < static_cast<float>(kMaxTones))) throw std::invalid_argument("sync: frequency range above 2^20 bins");
+  const long long syms = static_cast<long long>(t_max) + m.total - t_min;
+  if (syms > static_cast<long long>(kMaxSyms)) throw std::invalid_argument("sync: more than 65535 waterfall rows");
+  SyncGeometry g;
+  g.num_bins = static_cast<size_t>(bins) + m.tones + 1;
+  g.wf_syms = static_cast<size_t>(syms > 1 ? syms : 1);
+  g.wf_sample_start = t_min >= 0 ? static_cast<size_t>(t_min) * m.sps : 0;
+  g.sym_offset_adj = t_min < 0 ? -t_min : 0;
+  const int over = static_cast<int>(g.wf_syms) - m.total;
+  g.wf_t_max = over > 0 ? over : 0;
+  return g;
+}
+
+void Sync::set_rows_per_lane(int s) {
+  if (s != 0 && s != 1 && s != 2 && s != 4 && s != 8) throw std::invalid_argument("rows per lane: 0 (auto), 1, 2, 4 or 8");
+  rows_ = s;
+}
+
+// Measured (tools/sync_bench.py): sharing the phasor chain among rows pays
+// only once the launch still has about 32 waves per SIMD; below that one row per lane,
+// which spreads a call over the most waves, is fastest. 8 rows per lane never won.
+int Sync::rows_for(size_t num_syms, size_t num_tones, size_t nch) const {
+  if (rows_) return rows_;
+  const long long want = 32LL * 4 * device_cus();
+  for (int s = 4; s > 1; s /= 2)
+    if (static_cast<long long>((num_tones + 63) / 64) * ((num_syms + s - 1) / s) * nch >= want) return s;
+  return 1;
+}
+
+void Sync::waterfall(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,
+                     size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch, int mode,
+                     float* mag, hipStream_t s) {
+  if (mode != kWfLog && mode != kWfEnergy) throw std::invalid_argument("waterfall mode: ORION_WF_LOG / ORION_WF_ENERGY");
+  check_grid(nch, num_syms, num_tones);
+  if (samples_per_sym > 0x7fffffffu) throw std::invalid_argument("waterfall: samples_per_sym above 2^31 - 1");
+  if (n_per_ch > (1ull << 40) || time_offset > (1ull << 40)) throw std::invalid_argument("waterfall: length above 2^40");
+  if (num_syms == 0 || num_tones == 0) return;
+  if (num_tones != st_tones_ || fs != st_fs_ || base_hz != st_base_ || tone_spacing_hz != st_spacing_ ||
+      steps_.size() == 0) {
+    const std::vector<float> w = waterfall_steps(fs, base_hz, tone_spacing_hz, num_tones);
+    steps_.upload(w.data(), w.size() * sizeof(float), s);
+    st_tones_ = num_tones;
+    st_fs_ = fs;
+    st_base_ = base_hz;
+    st_spacing_ = tone_spacing_hz;
+  }
+  launch_waterfall(static_cast<const f2*>(iq), steps_.as<f2>(), mag, static_cast<int>(nch),
+                   static_cast<long long>(n_per_ch), static_cast<int>(samples_per_sym), static_cast<int>(num_syms),
+                   static_cast<int>(num_tones), static_cast<long long>(time_offset), mode,
+                   rows_for(num_syms, num_tones, nch), s);
+}
+
+void Sync::find_candidates(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, int t_min,
+                           int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, hipStream_t s) {
+  const Mode& m = mode_of(pattern);
+  // costas.rs:159: the reference reads heap[0] of an empty Vec when max_candidates == 0
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  check_grid(nch, num_syms, num_tones);
+  size_t cells = 0;
+  if (num_tones > static_cast<size_t>(m.tones) && t_max >= t_min) {
+    const unsigned long long nt = static_cast<unsigned long long>(static_cast<long long>(t_max) - t_min + 1);
+    const unsigned long long per = nt * (num_tones - m.tones + 1);
+    if (per > 0x7fffffffull || per * nch > (1ull << 33)) throw std::invalid_argument("costas search: too many cells");
+    cells = static_cast<size_t>(per) * nch;
+  }
+  score_.resize(cells * sizeof(float));
+  launch_costas_search(wf, score_.as<float>(), static_cast<int>(nch), static_cast<int>(num_syms),
+                       static_cast<int>(num_tones), m.pat, t_min, t_max, static_cast<int>(max_cand), cand, count, s);
+}
+
+void sync_llr(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, const SyncCandidate* cand,
+              const uint32_t* count, size_t max_cand, float* llr, hipStream_t s) {
+  mode_of(pattern);
+  if (max_cand == 0 || max_cand > kMaxCand) throw std::invalid_argument("1 <= max_cand <= 65536");
+  check_grid(nch, num_syms, num_tones);
+  launch_sync_llr(wf, static_cast<int>(nch), static_cast<int>(num_syms), static_cast<int>(num_tones),
+                  pattern == kCostasFt4, cand, count, static_cast<int>(max_cand), llr, nullptr, 0, s);
+}
+
+void Sync::sync(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                int t_min, int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr,
+                hipStream_t s) {
+  const Mode& m = mode_of(pattern);
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  const SyncGeometry g = sync_geometry(pattern, base_hz, max_hz, t_min, t_max);
+  check_grid(nch, g.wf_syms, g.num_bins);
+  wf_.resize(nch * g.wf_syms * g.num_bins * sizeof(float));
+  waterfall(iq, fs, base_hz, m.spacing, m.sps, g.wf_syms, g.num_bins, g.wf_sample_start, nch, n_per_ch, kWfLog,
+            wf_.as<float>(), s);
+  // ft8_sync.rs:130-143: the search runs over waterfall rows 0 ..= wf_t_max
+  find_candidates(wf_.as<float>(), nch, g.wf_syms, g.num_bins, pattern, 0, g.wf_t_max, max_cand, cand, count, s);
+  launch_sync_llr(wf_.as<float>(), static_cast<int>(nch), static_cast<int>(g.wf_syms), static_cast<int>(g.num_bins),
+                  pattern == kCostasFt4, cand, count, static_cast<int>(max_cand), llr, cand, g.sym_offset_adj, s);
+}
+
+void Sync::waterfall_host(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,
+                          size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch,
+                          int mode, float* mag) {
+  check_grid(nch, num_syms, num_tones);
+  const size_t ib = nch * n_per_ch * 8, ob = nch * num_syms * num_tones * sizeof(float);
+  h_iq_.resize(ib + 16);
+  h_out_.resize(ob + 16);
+  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  waterfall(h_iq_.as<void>(), fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones, time_offset, nch,
+            n_per_ch, mode, h_out_.as<float>(), nullptr);
+  if (ob) ORION_HIP(hipMemcpy(mag, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+void Sync::sync_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     int t_min, int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr) {
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
+  const size_t ib = nch * n_per_ch * 8;
+  const size_t cb = nch * max_cand * sizeof(SyncCandidate), nb = nch * sizeof(uint32_t);
+  const size_t lb = nch * max_cand * kSyncLlr * sizeof(float);
+  const size_t c_off = 0, n_off = (cb + 15) / 16 * 16;
+  h_iq_.resize(ib + 16);
+  h_cand_.resize(n_off + nb + 16);
+  h_out_.resize(lb + 16);
+  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  char* cbase = h_cand_.as<char>();
+  sync(pattern, h_iq_.as<void>(), nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand,
+       reinterpret_cast<SyncCandidate*>(cbase + c_off), reinterpret_cast<uint32_t*>(cbase + n_off),
+       h_out_.as<float>(), nullptr);
+  ORION_HIP(hipMemcpy(cand, cbase + c_off, cb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(count, cbase + n_off, nb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(llr, h_out_.as<void>(), lb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+}  // namespace orion

@@ -1,0 +1,66 @@
+// sync_blocks.hpp — the FT8 / FT4 sync front end over k_sync.hip (host side).
+//
+// Reference: sync/waterfall.rs (compute_waterfall), sync/costas.rs (find_candidates),
+// sync/ft8_sync.rs and sync/ft4_sync.rs (ft8_sync / ft4_sync). Not a Block: a sync call
+// has no streaming state and several outputs, so it has a handle of its own that owns
+// what the calls reuse (the step table, the scratch waterfall, the score map).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "blocks.hpp"
+
+namespace orion {
+
+enum : int { kWfLog = 0, kWfEnergy = 1 };       // include/orion_sdr_amd.h ORION_WF_*
+enum : int { kCostasFt8 = 0, kCostasFt4 = 1 };  // ORION_COSTAS_*
+
+// waterfall.rs:84-91: w_k = (cos phi, sin phi), phi = (-TAU * f) / fs, f = base + k *
+// spacing, all f32, libm sinf / cosf. Interleaved (re, im).
+std::vector<float> waterfall_steps(float fs, float base_hz, float tone_spacing_hz, size_t num_tones);
+
+// ft8_sync.rs:99-131 / ft4_sync.rs:74-98: the geometry a sync call derives.
+struct SyncGeometry {
+  size_t num_bins, wf_syms, wf_sample_start;
+  int sym_offset_adj, wf_t_max;
+};
+SyncGeometry sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max);
+
+class Sync {
+ public:
+  // Symbol rows per lane of the waterfall kernel: 1, 2, 4 or 8; 0 = chosen per call
+  // from the number of waves the call spreads over (1, 2 or 4).
+  void set_rows_per_lane(int s);
+  // All device pointers; asynchronous on s once the handle's buffers have grown to the
+  // geometry (growing frees and allocates, which synchronises the device).
+  void waterfall(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,
+                 size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch, int mode,
+                 float* mag, hipStream_t s);
+  void find_candidates(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, int t_min,
+                       int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, hipStream_t s);
+  void sync(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz, int t_min,
+            int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr, hipStream_t s);
+  // Host slices: uploaded, run as one device call, downloaded (synchronous).
+  void waterfall_host(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,
+                      size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch, int mode,
+                      float* mag);
+  void sync_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                 int t_min, int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr);
+
+ private:
+  int rows_for(size_t num_syms, size_t num_tones, size_t nch) const;
+  int rows_ = 0;
+  // the step table on the device and the geometry it was built for
+  DevBuf steps_;
+  float st_fs_ = 0, st_base_ = 0, st_spacing_ = 0;
+  size_t st_tones_ = 0;
+  DevBuf wf_, score_;             // sync()'s waterfall; the score map
+  DevBuf h_iq_, h_out_, h_cand_;  // staging of the host entries
+};
+
+// LLRs of caller-supplied candidates on a caller-supplied waterfall (device pointers).
+void sync_llr(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, const SyncCandidate* cand,
+              const uint32_t* count, size_t max_cand, float* llr, hipStream_t s);
+
+}  // namespace orion

@@ -30,6 +30,8 @@ __all__ = [
     "fir_lowpass_design", "kaiser_lowpass_taps",
     "kaiser_transition_norm", "kaiser_num_taps", "lp_cascade_design", "lib_path", "OrionError", "diag_stream_read",
     "AudioToIqChain", "IqToIqChain", "IqToAudioChain", "Graph", "stream_shard", "STREAM_HALO",
+    "SyncEngine", "CANDIDATE_DTYPE", "compute_waterfall", "find_candidates", "ft8_sync", "ft4_sync",
+    "ft8_sync_batch", "ft4_sync_batch", "sync_geometry",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -157,6 +159,16 @@ def _load():
         "orion_diag_stream_create": (vp, [C.c_uint32]), "orion_diag_stream_destroy": (i, [vp]),
         "orion_device_cus": (i, []),
         "orion_host_alloc": (vp, [sz]), "orion_host_free": (i, [vp]),
+        "orion_sync_new": (vp, []), "orion_sync_free": (None, [vp]), "orion_sync_set_rows_per_lane": (i, [vp, i]),
+        "orion_waterfall_compute": (i, [vp, vp, f, f, f, sz, sz, sz, sz, sz, sz, i, vp]),
+        "orion_waterfall_compute_device": (i, [vp, vp, f, f, f, sz, sz, sz, sz, sz, sz, i, vp, vp]),
+        "orion_costas_find_candidates_device": (i, [vp, vp, sz, sz, sz, i, i, i, sz, vp, vp, vp]),
+        "orion_sync_llr_device": (i, [vp, sz, sz, sz, i, vp, vp, sz, vp, vp]),
+        "orion_ft8_sync": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp]),
+        "orion_ft4_sync": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp]),
+        "orion_ft8_sync_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp, vp]),
+        "orion_ft4_sync_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp, vp]),
+        "orion_sync_geometry": (i, [i, f, f, i, i, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -848,6 +860,243 @@ def osc_table_phasors(freq_hz: float, fs: float, n: int, budget: int = 1 << 20):
     _check(_L.orion_osc_table_phasors(freq_hz, fs, int(budget), out.ctypes.data, out.size, C.byref(cs),
                                       C.byref(cl), C.byref(nt)))
     return out, int(cs.value), int(cl.value), int(nt.value)
+
+
+# ---- FT8 / FT4 frame sync (src/sync; src/python/ft8.rs) ------------------------
+CANDIDATE_DTYPE = np.dtype([("time_sym", np.int32), ("freq_bin", np.uint32), ("score", np.float32)])
+_PATTERNS = {"ft8": 0, "ft4": 1}
+_WF_MODES = {"log": 0, "energy": 1}
+SYNC_LLR = 174
+
+
+def sync_geometry(pattern: str, base_hz: float, max_hz: float, t_min: int, t_max: int):
+    """Host only: (num_bins, wf_syms, wf_sample_start, sym_offset_adj, wf_t_max) of an
+    ft8_sync / ft4_sync call (sync/ft8_sync.rs:99-131)."""
+    g = (C.c_size_t * 5)()
+    _check(_L.orion_sync_geometry(_PATTERNS[pattern], base_hz, max_hz, int(t_min), int(t_max), g))
+    return tuple(int(v) for v in g)
+
+
+class SyncEngine:
+    """The FT8 / FT4 sync front end on the GPU (include/orion_sdr_amd.h orion_sync): a
+    handle that keeps its step table, scratch waterfall and score map between calls.
+    IQ is complex64, 1-D (one channel) or (nch, n); numpy arrays or torch CUDA tensors.
+    The module-level compute_waterfall / find_candidates / ft8_sync / ft4_sync use one
+    shared engine."""
+
+    def __init__(self):
+        h = _L.orion_sync_new()
+        if not h:
+            raise OrionError(f"orion_sdr: construction failed: {_err()}")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.orion_sync_free(h)
+            self._h = None
+
+    def set_rows_per_lane(self, rows: int):
+        """Engine tuning: symbol rows per lane of the waterfall kernel (1, 2, 4, 8; 0 = auto)."""
+        _check(_L.orion_sync_set_rows_per_lane(self._h, int(rows)))
+        return self
+
+    @staticmethod
+    def _iq(iq):
+        """-> (array, nch, n, batched): a C-contiguous complex64 numpy array or CUDA tensor."""
+        if _is_torch(iq):
+            import torch
+
+            if not iq.is_cuda or not iq.is_contiguous():
+                raise ValueError("sync needs a contiguous CUDA tensor")
+            if iq.dtype != torch.complex64:
+                raise TypeError(f"expected torch.complex64, got {iq.dtype}")
+        else:
+            if not isinstance(iq, np.ndarray):
+                raise TypeError("sync expects a numpy array or a torch CUDA tensor")
+            if iq.dtype != np.complex64:
+                raise TypeError(f"expected complex64, got {iq.dtype}")
+            if not iq.flags["C_CONTIGUOUS"]:
+                raise ValueError("array is not C-contiguous")
+        if iq.ndim not in (1, 2):
+            raise ValueError(f"expected a 1-D or (nch, n) array, got {iq.ndim}-D")
+        if iq.ndim == 2 and iq.shape[0] < 1:
+            raise ValueError("expected at least one channel")
+        return iq, (1 if iq.ndim == 1 else iq.shape[0]), iq.shape[-1], iq.ndim == 2
+
+    @staticmethod
+    def _stream(x, stream):
+        import torch
+
+        return stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+
+    def compute_waterfall(self, iq, fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones,
+                          time_offset=0, mode="log", stream=None):
+        """compute_waterfall (sync/waterfall.rs:73-119): mag (num_syms, num_tones) float32
+        (with a leading nch axis for (nch, n) input). mode "log": ln(e + 1e-12); "energy":
+        the Goertzel energy e itself."""
+        iq, nch, n, batched = self._iq(iq)
+        shape = (nch, num_syms, num_tones) if batched else (num_syms, num_tones)
+        args = (float(fs), float(base_hz), float(tone_spacing_hz), int(samples_per_sym), int(num_syms),
+                int(num_tones), int(time_offset), nch, n, _WF_MODES[mode])
+        if _is_torch(iq):
+            import torch
+
+            mag = torch.empty(shape, dtype=torch.float32, device=iq.device)
+            _check(_L.orion_waterfall_compute_device(self._h, iq.data_ptr(), *args, mag.data_ptr(),
+                                                     self._stream(iq, stream)))
+            return mag
+        mag = np.empty(shape, np.float32)
+        _check(_L.orion_waterfall_compute(self._h, iq.ctypes.data, *args, mag.ctypes.data))
+        return mag
+
+    @staticmethod
+    def _wf(wf):
+        """-> (CUDA tensor, nch, num_syms, num_tones, batched); numpy is uploaded."""
+        import torch
+
+        if not _is_torch(wf):
+            wf = np.ascontiguousarray(wf, np.float32)
+            wf = torch.from_numpy(wf).cuda()
+        if not wf.is_cuda or not wf.is_contiguous() or wf.dtype != torch.float32:
+            raise ValueError("waterfall: a contiguous float32 array or CUDA tensor")
+        if wf.ndim not in (2, 3):
+            raise ValueError(f"waterfall: (num_syms, num_tones) or (nch, num_syms, num_tones), got {wf.ndim}-D")
+        return wf, (1 if wf.ndim == 2 else wf.shape[0]), wf.shape[-2], wf.shape[-1], wf.ndim == 3
+
+    def find_candidates_device(self, wf, pattern, t_min, t_max, max_cand, stream=None):
+        """The raw device call: (cand int32 tensor (nch, max_cand, 3) holding CANDIDATE_DTYPE
+        records, count uint32-as-int32 tensor (nch,)), asynchronous on the stream."""
+        import torch
+
+        wf, nch, ns, nt, _ = self._wf(wf)
+        cand = torch.empty((nch, max(int(max_cand), 1), 3), dtype=torch.int32, device=wf.device)
+        count = torch.empty((nch,), dtype=torch.int32, device=wf.device)
+        _check(_L.orion_costas_find_candidates_device(self._h, wf.data_ptr(), nch, ns, nt, _PATTERNS[pattern],
+                                                      int(t_min), int(t_max), int(max_cand), cand.data_ptr(),
+                                                      count.data_ptr(), self._stream(wf, stream)))
+        return cand, count
+
+    def find_candidates(self, wf, pattern, t_min, t_max, max_cand):
+        """find_candidates (sync/costas.rs:125-174; pattern "ft8") / find_ft4_candidates
+        (sync/ft4_sync.rs:122-163; "ft4") on a waterfall (numpy or CUDA tensor): a
+        CANDIDATE_DTYPE record array, best first, in the reference's order among equal
+        scores (a list of them, one per channel, for a 3-D waterfall)."""
+        cand, count = self.find_candidates_device(wf, pattern, t_min, t_max, max_cand)
+        c = cand.cpu().numpy().view(CANDIDATE_DTYPE)[..., 0]
+        k = count.cpu().numpy()
+        out = [c[ch, :k[ch]].copy() for ch in range(len(k))]
+        return out if wf.ndim == 3 else out[0]
+
+    def extract_llr(self, wf, pattern, cand):
+        """extract_*_llr + normalise_llr (sync/ft8_sync.rs:170-246, ft4_sync.rs:227-292) of
+        a CANDIDATE_DTYPE record array on a 2-D waterfall: float32 (len(cand), 174)."""
+        import torch
+
+        wf, nch, ns, nt, batched = self._wf(wf)
+        if batched:
+            raise ValueError("extract_llr: one channel at a time")
+        cand = np.ascontiguousarray(cand, CANDIDATE_DTYPE)
+        n = len(cand)
+        if n == 0:
+            return np.zeros((0, SYNC_LLR), np.float32)
+        dc = torch.from_numpy(cand.view(np.int32).reshape(n, 3).copy()).to(wf.device)
+        dn = torch.tensor([n], dtype=torch.int32, device=wf.device)
+        llr = torch.empty((n, SYNC_LLR), dtype=torch.float32, device=wf.device)
+        _check(_L.orion_sync_llr_device(wf.data_ptr(), 1, ns, nt, _PATTERNS[pattern], dc.data_ptr(), dn.data_ptr(), n,
+                                        llr.data_ptr(), self._stream(wf, None)))
+        return llr.cpu().numpy()
+
+    def sync_raw(self, pattern, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, stream=None):
+        """ft8_sync / ft4_sync as arrays: (cand (nch, max_cand) CANDIDATE_DTYPE, count (nch,),
+        llr (nch, max_cand, 174) float32), numpy whatever the input was."""
+        iq, nch, n, _ = self._iq(iq)
+        mc = int(max_cand)
+        args = (nch, n, float(fs), float(base_hz), float(max_hz), int(t_min), int(t_max), mc)
+        if _is_torch(iq):
+            import torch
+
+            fn = _L.orion_ft8_sync_device if pattern == "ft8" else _L.orion_ft4_sync_device
+            cand = torch.empty((nch, max(mc, 1), 3), dtype=torch.int32, device=iq.device)
+            count = torch.empty((nch,), dtype=torch.int32, device=iq.device)
+            llr = torch.empty((nch, max(mc, 1), SYNC_LLR), dtype=torch.float32, device=iq.device)
+            _check(fn(self._h, iq.data_ptr(), *args, cand.data_ptr(), count.data_ptr(), llr.data_ptr(),
+                      self._stream(iq, stream)))
+            return (cand.cpu().numpy().view(CANDIDATE_DTYPE)[..., 0], count.cpu().numpy().view(np.uint32),
+                    llr.cpu().numpy())
+        fn = _L.orion_ft8_sync if pattern == "ft8" else _L.orion_ft4_sync
+        cand = np.zeros((nch, max(mc, 1)), CANDIDATE_DTYPE)
+        count = np.zeros(nch, np.uint32)
+        llr = np.zeros((nch, max(mc, 1), SYNC_LLR), np.float32)
+        _check(fn(self._h, iq.ctypes.data, *args, cand.ctypes.data, count.ctypes.data, llr.ctypes.data))
+        return cand, count, llr
+
+    def _sync(self, pattern, iq, *a):
+        cand, count, llr = self.sync_raw(pattern, iq, *a)
+        out = [[{"time_sym": int(cand[ch, k]["time_sym"]), "freq_bin": int(cand[ch, k]["freq_bin"]),
+                 "score": float(cand[ch, k]["score"]), "llr": llr[ch, k].copy()} for k in range(int(count[ch]))]
+               for ch in range(len(count))]
+        return out
+
+    def ft8_sync(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+        """ft8_sync (sync/ft8_sync.rs:90-159; src/python/ft8.rs): list[dict] with keys
+        time_sym, freq_bin, score, llr (float32[174]), best first. iq: 1-D."""
+        if np.ndim(iq) != 1:
+            raise ValueError("ft8_sync expects a 1-D array (ft8_sync_batch takes (nch, n))")
+        return self._sync("ft8", iq, fs, base_hz, max_hz, t_min, t_max, max_cand)[0]
+
+    def ft4_sync(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+        """ft4_sync (sync/ft4_sync.rs:65-117): as ft8_sync."""
+        if np.ndim(iq) != 1:
+            raise ValueError("ft4_sync expects a 1-D array (ft4_sync_batch takes (nch, n))")
+        return self._sync("ft4", iq, fs, base_hz, max_hz, t_min, t_max, max_cand)[0]
+
+    def ft8_sync_batch(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+        """ft8_sync of every row of iq (nch, n) in one device call: a list per channel."""
+        if np.ndim(iq) != 2:
+            raise ValueError("ft8_sync_batch expects an (nch, n) array")
+        return self._sync("ft8", iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+    def ft4_sync_batch(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+        if np.ndim(iq) != 2:
+            raise ValueError("ft4_sync_batch expects an (nch, n) array")
+        return self._sync("ft4", iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+
+_SYNC = None
+
+
+def _sync_engine() -> SyncEngine:
+    global _SYNC
+    if _SYNC is None:
+        _SYNC = SyncEngine()
+    return _SYNC
+
+
+def compute_waterfall(iq, fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones, time_offset=0,
+                      mode="log"):
+    return _sync_engine().compute_waterfall(iq, fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones,
+                                            time_offset, mode)
+
+
+def find_candidates(wf, pattern, t_min, t_max, max_cand):
+    return _sync_engine().find_candidates(wf, pattern, t_min, t_max, max_cand)
+
+
+def ft8_sync(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+    return _sync_engine().ft8_sync(iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+
+def ft4_sync(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+    return _sync_engine().ft4_sync(iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+
+def ft8_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+    return _sync_engine().ft8_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+
+def ft4_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
+    return _sync_engine().ft4_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
