@@ -173,7 +173,10 @@ struct Dw {
 
 // New inputs of the tile whose staged sample 0 is x[porg]: x[porg + 8Q + 2l + 128k (+1)].
 // CLAMP = false (n >= 2 NEW): the uniform base is clamped into [0, n - NEW];
-// boundary tiles are rewritten exactly at staging. CLAMP: per-lane clamp.
+// boundary tiles are rewritten exactly at staging. CLAMP: per-lane clamp of each pair
+// into the whole pairs of [0, n): positions from n & ~1 on (the unpaired last sample of
+// an odd n included) are rewritten at staging. n = 1 holds no whole pair: nothing is
+// loaded, every position is rewritten.
 template <int Q, bool A16, bool CLAMP>
 __device__ __forceinline__ void dw_load(const f2* __restrict__ x, long long n, long long porg, int l,
                                         f2 (&v)[Dw<Q>::KL][2]) {
@@ -181,9 +184,14 @@ __device__ __forceinline__ void dw_load(const f2* __restrict__ x, long long n, l
   const f2* __restrict__ xb;
   int lo = 0, hi = 0;
   if constexpr (CLAMP) {
+    if (n < 2) {
+#pragma unroll
+      for (int k = 0; k < Dw<Q>::KL; ++k) v[k][0] = v[k][1] = f2{0.0f, 0.0f};
+      return;
+    }
     constexpr long long kSat = 1LL << 30;
     lo = static_cast<int>(max(-B, -kSat));
-    hi = static_cast<int>(min(max((n - 2 - B) & ~1LL, -kSat), kSat));
+    hi = static_cast<int>(min(max((n - 2 - B) & ~1LL, -kSat), kSat));  // >= lo (n >= 2, B even)
     xb = x + B;
   } else {
     xb = x + min(max(B, 0LL), (n - Dw<Q>::NEW) & ~1LL);
@@ -284,7 +292,7 @@ __device__ __forceinline__ void dw4_tile(f2* __restrict__ U, const float* __rest
 #pragma unroll 1
     for (int p = (n == 0 ? 0 : 8 * Q) + l; p < 8 * (D::TW + Q); p += 64) {
       const long long P = porg + p;
-      if (p < 8 * Q || !CLAMP || P < 0 || P >= nx) {
+      if (p < 8 * Q || !CLAMP || P < 0 || P >= (nx & ~1LL)) {  // clamped loads end at the last whole pair
         const int c = (-p) & 7;
         U[c * D::LRS + D::slot((p + c) / 8)] = load_hist(xc, nx, hc, hist_len, P);
       }

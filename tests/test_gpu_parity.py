@@ -426,10 +426,15 @@ def test_decimator_batch_geometries(gpu_lib, oracle, nch, n, chunk):
 def test_fir_lowpass(gpu_lib, oracle):
     F = gpu_lib.FirLowpass(1.25e6, 15e3, 10e3)
     report("fir golden nrmse", nrmse(F.process(GOLD["x_r"]), GOLD["fir_lowpass_out"]), 1e-6)
-    for args in [(1.25e6, 15e3, 10e3), (48e3, 3000.0, 800.0), (48e3, 5000.0, 150.0)]:  # 125 / 61 / 321 taps
+    # k_fir_real8<128> / <64> / <64> (trans_hz clamped to 0.2 pass_hz: 49 taps) / <256> /
+    # k_fir_real_generic
+    for *args, ntaps in [(1.25e6, 15e3, 10e3, 125), (48e3, 3000.0, 800.0, 61), (48e3, 5000.0, 150.0, 49),
+                         (48e3, 1000.0, 250.0, 193), (48e3, 500.0, 150.0, 321)]:
         x = RNG.standard_normal(200_000).astype(np.float32)
-        got = stream(gpu_lib.FirLowpass(*args), x, 77_777)
-        report(f"fir {len(oracle.fir_lowpass_taps(*args))} taps nrmse", nrmse(got, oracle.fir_lowpass(x, *args)), 1e-6)
+        F = gpu_lib.FirLowpass(*args)
+        assert len(F.taps()) == len(oracle.fir_lowpass_taps(*args)) == ntaps
+        got = stream(F, x, 77_777)
+        report(f"fir {ntaps} taps nrmse", nrmse(got, oracle.fir_lowpass(x, *args)), 1e-6)
     # k_fir_real8 tile geometry (4096 outputs per tile as two 2048-output halves)
     x = RNG.standard_normal(3 * 4096 + 77).astype(np.float32)
     ref = oracle.fir_lowpass(x, 1.25e6, 15e3, 10e3)
