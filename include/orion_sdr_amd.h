@@ -417,6 +417,81 @@ int orion_ft4_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_pe
  * geom[5] = num_bins, wf_syms, wf_sample_start, sym_offset_adj, wf_t_max. */
 int orion_sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max, size_t geom[5]);
 
+/* ---- FT8 / FT4 channel codec: LDPC(174,91) + CRC-14 (src/codec) -------------------
+ * The decode half of the receive path: 174 LLRs (positive: the bit is more likely 0) ->
+ * belief propagation (ldpc_decode_soft, ldpc.rs:673-757) -> CRC-14 over the 77-bit payload
+ * (ft8.rs:91-130, ft4.rs:91-127). protocol: ORION_COSTAS_FT8 / ORION_COSTAS_FT4 (FT4
+ * un-XORs the payload, ft4.rs:22).
+ * rule: ORION_LDPC_RULE_REFERENCE is the reference's arithmetic bit for bit, plain word,
+ * error count and iterations included. Its check -> bit message has the wrong sign for a
+ * check with 7 entries (24 of the 83), so it does not correct errors: it decodes a word
+ * whose initial hard decision is already valid. ORION_LDPC_RULE_SUM_PRODUCT differs in
+ * that one constant (+2 atanh(a) for those checks) and does correct errors. DESIGN.md 8.1.
+ * max_iter <= 255; 20 is the reference's. A bad protocol, rule or max_iter: ORION_E_ARG. */
+#define ORION_LDPC_N 174
+#define ORION_LDPC_RULE_REFERENCE 0
+#define ORION_LDPC_RULE_SUM_PRODUCT 1
+#define ORION_LDPC_PARITY_FAILED 0 /* status: unsatisfied checks remain */
+#define ORION_LDPC_CRC_MISMATCH 1  /* all checks satisfied, the CRC is not */
+#define ORION_LDPC_DECODED 2
+typedef struct {
+  uint8_t payload[10]; /* status 2: the 77 bits MSB first, byte 9 & 0xF8; else zeros */
+  uint8_t status;
+  uint8_t iterations;  /* 0: the initial decision was valid (or max_iter == 0); else iterations started */
+  uint16_t errors;     /* unsatisfied checks of the best word */
+  uint16_t pad;
+} orion_ldpc_result;
+/* Each channel's pick, as Ft8StreamDecoder::decode_buf makes it (ft8.rs:302-320). */
+typedef struct {
+  int32_t first_ok;  /* index of the first candidate with status 2, or -1 */
+  float carrier_hz;  /* base_hz + freq_bin * tone spacing in f32; 0 when first_ok < 0 */
+  float snr_db;      /* that candidate's score */
+  uint32_t pad;
+} orion_decode_pick;
+/* n codewords, llr [n][174] -> results [n], plain [n][174] (the best hard decision; may be
+ * NULL). count non-NULL: llr is the [nch][max_cand][174] layout of orion_ft*_sync with
+ * n = nch * max_cand, and slots at or past count[ch] give all-zero records (and plain)
+ * without being decoded; count NULL: max_cand is ignored. One kernel, one wave64
+ * workgroup per codeword. Host slices (synchronous) / device buffers (asynchronous). */
+int orion_ldpc_decode(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                      size_t max_iter, orion_ldpc_result* results, uint8_t* plain);
+int orion_ldpc_decode_device(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                             size_t max_iter, orion_ldpc_result* results, uint8_t* plain, void* stream);
+/* orion_ft*_sync, then the decode of every candidate and each channel's pick, on one
+ * stream with no host round trip. cand, count, llr as orion_ft*_sync writes them (llr may
+ * be NULL in the host-slice calls); results [nch][max_cand]; pick [nch]. */
+int orion_ft8_decode(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                     uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick);
+int orion_ft8_decode_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter,
+                            orion_candidate* cand, uint32_t* count, float* llr, orion_ldpc_result* results,
+                            orion_decode_pick* pick, void* stream);
+int orion_ft4_decode(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                     uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick);
+int orion_ft4_decode_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter,
+                            orion_candidate* cand, uint32_t* count, float* llr, orion_ldpc_result* results,
+                            orion_decode_pick* pick, void* stream);
+/* Host only (no device is touched). */
+/* Ft8Codec::encode, ft8.rs:29-59: tones[58]; Ft4Codec::encode, ft4.rs:29-65: tones[87].
+ * a91_xor (12 bytes, may be NULL) is XORed into the 91-bit block after the CRC is
+ * appended: test frames whose parity passes and whose CRC does not. */
+int orion_ft8_encode(const uint8_t payload[10], uint8_t tones[58], const uint8_t* a91_xor);
+int orion_ft4_encode(const uint8_t payload[10], uint8_t tones[87], const uint8_t* a91_xor);
+/* frame_to_llr_hard, ft8.rs:79-89 / ft4.rs:79-89: +-10 per bit. */
+int orion_ft_frame_to_llr_hard(int protocol, const uint8_t* tones, float llr[174]);
+/* The scalar decoder the device kernel is held to: one codeword, same record. plain may be NULL. */
+int orion_ldpc_decode_host(const float llr[174], int protocol, int rule, size_t max_iter, orion_ldpc_result* result,
+                           uint8_t* plain);
+/* ft8_crc14, crc.rs:37-54, over the first num_bits bits of message (MSB first). */
+uint16_t orion_ft_crc14(const uint8_t* message, size_t num_bits);
+/* The code's tables: the edge list as stated (edges [522][2]: check, bit; 0-based) and what
+ * is derived from it: row_start [84], bit_check [174][3] (ascending), generator [83][12]
+ * (rows bit-packed MSB first). Any pointer may be NULL. */
+int orion_ldpc_tables(uint8_t* edges, uint16_t* row_start, uint8_t* bit_check, uint8_t* generator);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "blocks.hpp"
+#include "ldpc.hpp"
 #include "osc.hpp"
 #include "scan_blocks.hpp"
 #include "sync_blocks.hpp"
@@ -21,6 +22,12 @@ struct orion_sync {
 };
 static_assert(sizeof(orion_candidate) == sizeof(orion::SyncCandidate) && sizeof(orion_candidate) == 12,
               "orion_candidate is the kernels' record");
+static_assert(sizeof(orion_ldpc_result) == sizeof(orion::ldpc::Result) && sizeof(orion_ldpc_result) == 16 &&
+                  sizeof(orion_decode_pick) == sizeof(orion::DecodePick) && sizeof(orion_decode_pick) == 16,
+              "orion_ldpc_result / orion_decode_pick are the kernels' records");
+static_assert(ORION_LDPC_N == orion::ldpc::kN && ORION_LDPC_RULE_SUM_PRODUCT == orion::ldpc::kRuleSumProduct &&
+                  ORION_LDPC_DECODED == orion::ldpc::kDecoded && ORION_COSTAS_FT4 == orion::ldpc::kFt4,
+              "the header's constants are ldpc.hpp's");
 
 namespace {
 thread_local std::string g_err;
@@ -684,6 +691,123 @@ int orion_sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int
     geom[2] = g.wf_sample_start;
     geom[3] = static_cast<size_t>(g.sym_offset_adj);
     geom[4] = static_cast<size_t>(g.wf_t_max);
+    return ORION_OK;
+  });
+}
+
+/* ---- FT8 / FT4 channel codec (ldpc.hpp, k_ldpc.hip) ---- */
+int orion_ldpc_decode(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                      size_t max_iter, orion_ldpc_result* results, uint8_t* plain) {
+  if (n && (!llr || !results)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc_decode_host(llr, n, count, max_cand, protocol, rule, max_iter, results, plain);
+    return ORION_OK;
+  });
+}
+int orion_ldpc_decode_device(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                             size_t max_iter, orion_ldpc_result* results, uint8_t* plain, void* stream) {
+  if (n && (!llr || !results)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc_decode(llr, n, count, max_cand, protocol, rule, max_iter, results, plain,
+                       static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+namespace {
+int decode_device(int pattern, orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                  float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                  uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || !pick || (max_cand && (!cand || !llr || !results)))
+    return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.decode(pattern, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
+                   reinterpret_cast<orion::SyncCandidate*>(cand), count, llr, results,
+                   reinterpret_cast<orion::DecodePick*>(pick), static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int decode_host(int pattern, orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || !pick || (max_cand && (!cand || !results))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.decode_host(pattern, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
+                        reinterpret_cast<orion::SyncCandidate*>(cand), count, llr, results,
+                        reinterpret_cast<orion::DecodePick*>(pick));
+    return ORION_OK;
+  });
+}
+}  // namespace
+int orion_ft8_decode(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                     uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick) {
+  return decode_host(ORION_COSTAS_FT8, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
+                     cand, count, llr, results, pick);
+}
+int orion_ft8_decode_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter,
+                            orion_candidate* cand, uint32_t* count, float* llr, orion_ldpc_result* results,
+                            orion_decode_pick* pick, void* stream) {
+  return decode_device(ORION_COSTAS_FT8, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule,
+                       max_iter, cand, count, llr, results, pick, stream);
+}
+int orion_ft4_decode(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, orion_candidate* cand,
+                     uint32_t* count, float* llr, orion_ldpc_result* results, orion_decode_pick* pick) {
+  return decode_host(ORION_COSTAS_FT4, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
+                     cand, count, llr, results, pick);
+}
+int orion_ft4_decode_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, int t_min, int t_max, size_t max_cand, int rule, size_t max_iter,
+                            orion_candidate* cand, uint32_t* count, float* llr, orion_ldpc_result* results,
+                            orion_decode_pick* pick, void* stream) {
+  return decode_device(ORION_COSTAS_FT4, h, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule,
+                       max_iter, cand, count, llr, results, pick, stream);
+}
+int orion_ft8_encode(const uint8_t payload[10], uint8_t tones[58], const uint8_t* a91_xor) {
+  if (!payload || !tones) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc::encode_tones(orion::ldpc::kFt8, payload, tones, a91_xor);
+    return ORION_OK;
+  });
+}
+int orion_ft4_encode(const uint8_t payload[10], uint8_t tones[87], const uint8_t* a91_xor) {
+  if (!payload || !tones) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc::encode_tones(orion::ldpc::kFt4, payload, tones, a91_xor);
+    return ORION_OK;
+  });
+}
+int orion_ft_frame_to_llr_hard(int protocol, const uint8_t* tones, float llr[174]) {
+  if (!tones || !llr) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc::frame_to_llr_hard(protocol, tones, llr);
+    return ORION_OK;
+  });
+}
+int orion_ldpc_decode_host(const float llr[174], int protocol, int rule, size_t max_iter, orion_ldpc_result* result,
+                           uint8_t* plain) {
+  if (!llr || !result) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpc::check_args(protocol, rule, max_iter);
+    orion::ldpc::decode_payload(protocol, llr, static_cast<int>(max_iter), rule,
+                                reinterpret_cast<orion::ldpc::Result*>(result), plain);
+    return ORION_OK;
+  });
+}
+uint16_t orion_ft_crc14(const uint8_t* message, size_t num_bits) {
+  if (!message || num_bits > (1u << 20)) return 0;
+  return orion::ldpc::crc14(message, static_cast<int>(num_bits));
+}
+int orion_ldpc_tables(uint8_t* edges, uint16_t* row_start, uint8_t* bit_check, uint8_t* generator) {
+  return guarded([&] {
+    const orion::ldpc::Tables& t = orion::ldpc::tables();
+    if (edges) std::memcpy(edges, orion::ldpc::kEdge, sizeof orion::ldpc::kEdge);
+    if (row_start) std::memcpy(row_start, t.row_start, sizeof t.row_start);
+    if (bit_check) std::memcpy(bit_check, t.bit_check, sizeof t.bit_check);
+    if (generator) std::memcpy(generator, t.generator, sizeof t.generator);
     return ORION_OK;
   });
 }

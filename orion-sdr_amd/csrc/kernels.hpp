@@ -203,4 +203,19 @@ void launch_costas_search(const float* wf_dev, float* score_dev, int nch, int nu
 void launch_sync_llr(const float* wf_dev, int nch, int num_syms, int num_tones, bool ft4, const SyncCandidate* cand_dev,
                      const uint32_t* count_dev, int max_cand, float* llr_dev, SyncCandidate* cand_out_dev, int sym_adj,
                      hipStream_t s);
+
+// ------------------------------------------ LDPC(174,91) + CRC-14 decode (k_ldpc.hip) --
+// n codewords, llr_dev [n][174] -> res_dev [n] records of 16 bytes (ldpc.hpp Result, 4-byte
+// aligned), plain_dev [n][174] u8 or null. count_dev (optional): the sync layout, codeword
+// w is slot w % max_cand of channel w / max_cand; slots at or past count[channel] give an
+// all-zero record and are not decoded. rule / max_iter: ldpc.hpp (max_iter <= 255).
+void launch_ldpc_decode(const float* llr_dev, long long n, const uint32_t* count_dev, int max_cand, bool ft4, int rule,
+                        int max_iter, void* res_dev, uint8_t* plain_dev, hipStream_t s);
+struct DecodePick {  // include/orion_sdr_amd.h orion_decode_pick
+  int32_t first_ok;  // the first candidate with status 2, or -1
+  float carrier_hz, snr_db;
+  uint32_t pad;
+};
+void launch_decode_pick(const SyncCandidate* cand_dev, const uint32_t* count_dev, const void* res_dev, int nch,
+                        int max_cand, float base_hz, float spacing, DecodePick* pick_dev, hipStream_t s);
 }  // namespace orion

@@ -4,6 +4,8 @@
 #include <cmath>
 #include <stdexcept>
 
+#include "ldpc.hpp"
+
 namespace orion {
 
 namespace {
@@ -143,6 +145,76 @@ void Sync::sync(int pattern, const void* iq, size_t nch, size_t n_per_ch, float 
   find_candidates(wf_.as<float>(), nch, g.wf_syms, g.num_bins, pattern, 0, g.wf_t_max, max_cand, cand, count, s);
   launch_sync_llr(wf_.as<float>(), static_cast<int>(nch), static_cast<int>(g.wf_syms), static_cast<int>(g.num_bins),
                   pattern == kCostasFt4, cand, count, static_cast<int>(max_cand), llr, cand, g.sym_offset_adj, s);
+}
+
+void ldpc_decode(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                 size_t max_iter, void* results, uint8_t* plain, hipStream_t s) {
+  ldpc::check_args(protocol, rule, max_iter);
+  if (n > 0x7fffffffull) throw std::invalid_argument("ldpc decode: more than 2^31 - 1 codewords");
+  if (count && (max_cand == 0 || max_cand > kMaxCand || n % max_cand != 0))
+    throw std::invalid_argument("ldpc decode: with count, n = nch * max_cand and 1 <= max_cand <= 65536");
+  if (reinterpret_cast<uintptr_t>(results) % 4) throw std::invalid_argument("ldpc decode: results not 4-byte aligned");
+  launch_ldpc_decode(llr, static_cast<long long>(n), count, static_cast<int>(count ? max_cand : 1),
+                     protocol == ldpc::kFt4, rule, static_cast<int>(max_iter), results, plain, s);
+}
+
+void ldpc_decode_host(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                      size_t max_iter, void* results, uint8_t* plain) {
+  ldpc::check_args(protocol, rule, max_iter);
+  if (count && (max_cand == 0 || n % max_cand != 0))
+    throw std::invalid_argument("ldpc decode: with count, n = nch * max_cand and max_cand >= 1");
+  if (n == 0) return;
+  const size_t lb = n * ldpc::kN * sizeof(float), rb = n * sizeof(ldpc::Result), pb = plain ? n * ldpc::kN : 0;
+  const size_t nb = count ? n / max_cand * sizeof(uint32_t) : 0;
+  DevBuf d_llr(lb), d_res(rb), d_plain(pb + 16), d_count(nb + 16);
+  ORION_HIP(hipMemcpy(d_llr.as<void>(), llr, lb, hipMemcpyHostToDevice));
+  if (nb) ORION_HIP(hipMemcpy(d_count.as<void>(), count, nb, hipMemcpyHostToDevice));
+  ldpc_decode(d_llr.as<float>(), n, count ? d_count.as<uint32_t>() : nullptr, max_cand, protocol, rule, max_iter,
+              d_res.as<void>(), plain ? d_plain.as<uint8_t>() : nullptr, nullptr);
+  ORION_HIP(hipMemcpy(results, d_res.as<void>(), rb, hipMemcpyDeviceToHost));
+  if (pb) ORION_HIP(hipMemcpy(plain, d_plain.as<void>(), pb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+void Sync::decode(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                  int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, SyncCandidate* cand, uint32_t* count,
+                  float* llr, void* results, DecodePick* pick, hipStream_t s) {
+  const Mode& m = mode_of(pattern);
+  ldpc::check_args(pattern, rule, max_iter);
+  sync(pattern, iq, nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, cand, count, llr, s);
+  ldpc_decode(llr, nch * max_cand, count, max_cand, pattern, rule, max_iter, results, nullptr, s);
+  launch_decode_pick(cand, count, results, static_cast<int>(nch), static_cast<int>(max_cand), base_hz, m.spacing, pick,
+                     s);
+}
+
+void Sync::decode_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                       int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, SyncCandidate* cand,
+                       uint32_t* count, float* llr, void* results, DecodePick* pick) {
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
+  ldpc::check_args(pattern, rule, max_iter);
+  const size_t ib = nch * n_per_ch * 8;
+  const size_t cb = nch * max_cand * sizeof(SyncCandidate), nb = nch * sizeof(uint32_t);
+  const size_t lb = nch * max_cand * kSyncLlr * sizeof(float);
+  const size_t rb = nch * max_cand * sizeof(ldpc::Result), kb = nch * sizeof(DecodePick);
+  const size_t n_off = (cb + 15) / 16 * 16, k_off = (rb + 15) / 16 * 16;
+  h_iq_.resize(ib + 16);
+  h_cand_.resize(n_off + nb + 16);
+  h_out_.resize(lb + 16);
+  h_res_.resize(k_off + kb + 16);
+  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  char* cbase = h_cand_.as<char>();
+  char* rbase = h_res_.as<char>();
+  decode(pattern, h_iq_.as<void>(), nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
+         reinterpret_cast<SyncCandidate*>(cbase), reinterpret_cast<uint32_t*>(cbase + n_off), h_out_.as<float>(), rbase,
+         reinterpret_cast<DecodePick*>(rbase + k_off), nullptr);
+  ORION_HIP(hipMemcpy(cand, cbase, cb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(count, cbase + n_off, nb, hipMemcpyDeviceToHost));
+  if (llr) ORION_HIP(hipMemcpy(llr, h_out_.as<void>(), lb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(results, rbase, rb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(pick, rbase + k_off, kb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
 }
 
 void Sync::waterfall_host(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,

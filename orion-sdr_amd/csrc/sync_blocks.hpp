@@ -41,6 +41,15 @@ class Sync {
                        int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, hipStream_t s);
   void sync(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz, int t_min,
             int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr, hipStream_t s);
+  // sync, then the LDPC + CRC decode of every candidate (ldpc_decode below) and the pick
+  // of each channel's first decoded one, all on s with no host round trip. results
+  // [nch][max_cand] records, pick [nch].
+  void decode(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz, int t_min,
+              int t_max, size_t max_cand, int rule, size_t max_iter, SyncCandidate* cand, uint32_t* count, float* llr,
+              void* results, DecodePick* pick, hipStream_t s);
+  void decode_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                   int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, SyncCandidate* cand, uint32_t* count,
+                   float* llr, void* results, DecodePick* pick);
   // Host slices: uploaded, run as one device call, downloaded (synchronous).
   void waterfall_host(const void* iq, float fs, float base_hz, float tone_spacing_hz, size_t samples_per_sym,
                       size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch, int mode,
@@ -56,11 +65,22 @@ class Sync {
   float st_fs_ = 0, st_base_ = 0, st_spacing_ = 0;
   size_t st_tones_ = 0;
   DevBuf wf_, score_;             // sync()'s waterfall; the score map
-  DevBuf h_iq_, h_out_, h_cand_;  // staging of the host entries
+  DevBuf h_iq_, h_out_, h_cand_, h_res_;  // staging of the host entries
 };
 
 // LLRs of caller-supplied candidates on a caller-supplied waterfall (device pointers).
 void sync_llr(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, const SyncCandidate* cand,
               const uint32_t* count, size_t max_cand, float* llr, hipStream_t s);
+
+
+// LDPC(174,91) + CRC-14 decode (k_ldpc.hip; ldpc.hpp for the rule and the record) of n
+// codewords, llr [n][174] -> results [n] (16-byte records), plain [n][174] u8 or null;
+// device pointers, asynchronous on s. count non-null: the layout sync() writes, n = nch *
+// max_cand, and the slots past a channel's count give all-zero records without a decode.
+void ldpc_decode(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                 size_t max_iter, void* results, uint8_t* plain, hipStream_t s);
+// Host slices (count: nch = n / max_cand entries, or null): synchronous.
+void ldpc_decode_host(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
+                      size_t max_iter, void* results, uint8_t* plain);
 
 }  // namespace orion

@@ -32,6 +32,8 @@ __all__ = [
     "AudioToIqChain", "IqToIqChain", "IqToAudioChain", "Graph", "stream_shard", "STREAM_HALO",
     "SyncEngine", "CANDIDATE_DTYPE", "compute_waterfall", "find_candidates", "ft8_sync", "ft4_sync",
     "ft8_sync_batch", "ft4_sync_batch", "sync_geometry",
+    "Ft8Codec", "Ft4Codec", "RESULT_DTYPE", "PICK_DTYPE", "LDPC_N", "ldpc_decode_batch", "ldpc_decode_host",
+    "ldpc_tables", "ft_crc14", "ft8_decode", "ft4_decode", "ft8_decode_batch", "ft4_decode_batch",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,6 +171,17 @@ def _load():
         "orion_ft8_sync_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp, vp]),
         "orion_ft4_sync_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, vp, vp, vp, vp]),
         "orion_sync_geometry": (i, [i, f, f, i, i, C.POINTER(sz)]),
+        "orion_ldpc_decode": (i, [vp, sz, vp, sz, i, i, sz, vp, vp]),
+        "orion_ldpc_decode_device": (i, [vp, sz, vp, sz, i, i, sz, vp, vp, vp]),
+        "orion_ft8_decode": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, i, sz, vp, vp, vp, vp, vp]),
+        "orion_ft4_decode": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, i, sz, vp, vp, vp, vp, vp]),
+        "orion_ft8_decode_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, i, sz, vp, vp, vp, vp, vp, vp]),
+        "orion_ft4_decode_device": (i, [vp, vp, sz, sz, f, f, f, i, i, sz, i, sz, vp, vp, vp, vp, vp, vp]),
+        "orion_ft8_encode": (i, [vp, vp, vp]), "orion_ft4_encode": (i, [vp, vp, vp]),
+        "orion_ft_frame_to_llr_hard": (i, [i, vp, vp]),
+        "orion_ldpc_decode_host": (i, [vp, i, i, sz, vp, vp]),
+        "orion_ft_crc14": (C.c_uint16, [vp, sz]),
+        "orion_ldpc_tables": (i, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -867,6 +880,17 @@ CANDIDATE_DTYPE = np.dtype([("time_sym", np.int32), ("freq_bin", np.uint32), ("s
 _PATTERNS = {"ft8": 0, "ft4": 1}
 _WF_MODES = {"log": 0, "energy": 1}
 SYNC_LLR = 174
+LDPC_N = 174
+# include/orion_sdr_amd.h orion_ldpc_result / orion_decode_pick
+RESULT_DTYPE = np.dtype([("payload", np.uint8, (10,)), ("status", np.uint8), ("iterations", np.uint8),
+                         ("errors", np.uint16), ("pad", np.uint16)])
+PICK_DTYPE = np.dtype([("first_ok", np.int32), ("carrier_hz", np.float32), ("snr_db", np.float32), ("pad", np.uint32)])
+_RULES = {"reference": 0, "sum_product": 1}
+
+
+def _rule(rule) -> int:
+    """A rule name, or a number passed through for the library to judge."""
+    return _RULES[rule] if rule in _RULES else int(rule)
 
 
 def sync_geometry(pattern: str, base_hz: float, max_hz: float, t_min: int, t_max: int):
@@ -1063,6 +1087,79 @@ class SyncEngine:
         return self._sync("ft4", iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
 
 
+    def decode_raw(self, pattern, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20,
+                   stream=None):
+        """ft8_decode / ft4_decode as arrays: (cand, count, llr, results (nch, max_cand)
+        RESULT_DTYPE, pick (nch,) PICK_DTYPE), numpy whatever the input was. One device call:
+        sync, the LDPC + CRC decode of every candidate and the pick, on one stream."""
+        iq, nch, n, _ = self._iq(iq)
+        mc = int(max_cand)
+        args = (nch, n, float(fs), float(base_hz), float(max_hz), int(t_min), int(t_max), mc, _rule(rule), int(max_iter))
+        if _is_torch(iq):
+            import torch
+
+            fn = _L.orion_ft8_decode_device if pattern == "ft8" else _L.orion_ft4_decode_device
+            cand = torch.empty((nch, max(mc, 1), 3), dtype=torch.int32, device=iq.device)
+            count = torch.empty((nch,), dtype=torch.int32, device=iq.device)
+            llr = torch.empty((nch, max(mc, 1), SYNC_LLR), dtype=torch.float32, device=iq.device)
+            res = torch.empty((nch, max(mc, 1), 4), dtype=torch.int32, device=iq.device)
+            pick = torch.empty((nch, 4), dtype=torch.int32, device=iq.device)
+            _check(fn(self._h, iq.data_ptr(), *args, cand.data_ptr(), count.data_ptr(), llr.data_ptr(), res.data_ptr(),
+                      pick.data_ptr(), self._stream(iq, stream)))
+            return (cand.cpu().numpy().view(CANDIDATE_DTYPE)[..., 0], count.cpu().numpy().view(np.uint32),
+                    llr.cpu().numpy(), res.cpu().numpy().view(RESULT_DTYPE)[..., 0],
+                    pick.cpu().numpy().view(PICK_DTYPE)[..., 0])
+        fn = _L.orion_ft8_decode if pattern == "ft8" else _L.orion_ft4_decode
+        cand = np.zeros((nch, max(mc, 1)), CANDIDATE_DTYPE)
+        count = np.zeros(nch, np.uint32)
+        llr = np.zeros((nch, max(mc, 1), SYNC_LLR), np.float32)
+        res = np.zeros((nch, max(mc, 1)), RESULT_DTYPE)
+        pick = np.zeros(nch, PICK_DTYPE)
+        _check(fn(self._h, iq.ctypes.data, *args, cand.ctypes.data, count.ctypes.data, llr.ctypes.data,
+                  res.ctypes.data, pick.ctypes.data))
+        return cand, count, llr, res, pick
+
+    def _decode(self, pattern, iq, *a, **kw):
+        cand, count, llr, res, pick = self.decode_raw(pattern, iq, *a, **kw)
+        out = []
+        for ch in range(len(count)):
+            k = int(count[ch])
+            fo = int(pick[ch]["first_ok"])
+            out.append({
+                "candidates": [{"time_sym": int(c["time_sym"]), "freq_bin": int(c["freq_bin"]), "score": float(c["score"])}
+                               for c in cand[ch, :k]],
+                "llr": llr[ch, :k].copy(), "results": res[ch, :k].copy(), "first_ok": fo,
+                "payload": res[ch, fo]["payload"].tobytes() if fo >= 0 else None,
+                "carrier_hz": float(pick[ch]["carrier_hz"]) if fo >= 0 else None,
+                "snr_db": float(pick[ch]["snr_db"]) if fo >= 0 else None})
+        return out
+
+    def ft8_decode(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+        """ft8_sync, then Ft8Codec::decode_soft of every candidate on the device, and the
+        reference stream decoder's pick (codec/ft8.rs:252-323): a dict with candidates,
+        llr, results (RESULT_DTYPE), first_ok (the first candidate with status 2, or -1)
+        and its payload (bytes), carrier_hz and snr_db (None when first_ok is -1). iq: 1-D."""
+        if np.ndim(iq) != 1:
+            raise ValueError("ft8_decode expects a 1-D array (ft8_decode_batch takes (nch, n))")
+        return self._decode("ft8", iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule=rule, max_iter=max_iter)[0]
+
+    def ft4_decode(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+        if np.ndim(iq) != 1:
+            raise ValueError("ft4_decode expects a 1-D array (ft4_decode_batch takes (nch, n))")
+        return self._decode("ft4", iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule=rule, max_iter=max_iter)[0]
+
+    def ft8_decode_batch(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+        """ft8_decode of every row of iq (nch, n) in one device call: a dict per channel."""
+        if np.ndim(iq) != 2:
+            raise ValueError("ft8_decode_batch expects an (nch, n) array")
+        return self._decode("ft8", iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule=rule, max_iter=max_iter)
+
+    def ft4_decode_batch(self, iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+        if np.ndim(iq) != 2:
+            raise ValueError("ft4_decode_batch expects an (nch, n) array")
+        return self._decode("ft4", iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule=rule, max_iter=max_iter)
+
+
 _SYNC = None
 
 
@@ -1097,6 +1194,159 @@ def ft8_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
 
 def ft4_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand):
     return _sync_engine().ft4_sync_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand)
+
+
+def ft8_decode(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+    return _sync_engine().ft8_decode(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter)
+
+
+def ft4_decode(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+    return _sync_engine().ft4_decode(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter)
+
+
+def ft8_decode_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+    return _sync_engine().ft8_decode_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter)
+
+
+def ft4_decode_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule="reference", max_iter=20):
+    return _sync_engine().ft4_decode_batch(iq, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter)
+
+
+# ---- FT8 / FT4 channel codec: LDPC(174,91) + CRC-14 (src/codec; src/python/ft8.rs) ----
+def ft_crc14(message: bytes, num_bits: int) -> int:
+    """ft8_crc14 (codec/crc.rs:37-54) over the first num_bits bits of message."""
+    message = bytes(message)
+    if num_bits < 0 or num_bits > 8 * len(message):
+        raise ValueError("num_bits beyond the message")
+    return int(_L.orion_ft_crc14(message, int(num_bits)))
+
+
+def ldpc_tables():
+    """Host only: the code's edge list as the library states it and the tables it derives:
+    (edges (522, 2) uint8 [check, bit], row_start (84,) uint16, bit_check (174, 3) uint8,
+    generator (83, 12) uint8)."""
+    edges = np.zeros((522, 2), np.uint8)
+    row_start = np.zeros(84, np.uint16)
+    bit_check = np.zeros((LDPC_N, 3), np.uint8)
+    gen = np.zeros((83, 12), np.uint8)
+    _check(_L.orion_ldpc_tables(edges.ctypes.data, row_start.ctypes.data, bit_check.ctypes.data, gen.ctypes.data))
+    return edges, row_start, bit_check, gen
+
+
+def _llr174(llr) -> np.ndarray:
+    if not isinstance(llr, np.ndarray) or llr.dtype != np.float32 or llr.shape != (LDPC_N,):
+        raise ValueError("expected a float32 array of 174 LLRs")
+    return np.ascontiguousarray(llr)
+
+
+def ldpc_decode_host(llr, protocol="ft8", rule="reference", max_iter=20):
+    """The library's scalar decoder (host only; what the kernel is held to) on one
+    codeword: (result: a RESULT_DTYPE record, plain uint8[174])."""
+    llr = _llr174(llr)
+    res = np.zeros(1, RESULT_DTYPE)
+    plain = np.zeros(LDPC_N, np.uint8)
+    _check(_L.orion_ldpc_decode_host(llr.ctypes.data, _PATTERNS[protocol], _rule(rule), int(max_iter), res.ctypes.data,
+                                     plain.ctypes.data))
+    return res[0], plain
+
+
+def ldpc_decode_batch(llr, protocol, rule="reference", max_iter=20, return_plain=False, count=None, stream=None):
+    """LDPC(174,91) belief propagation + CRC-14 of a batch of codewords on the GPU, one
+    wave64 workgroup each: llr float32 [..., 174] (numpy array or torch CUDA tensor) ->
+    a RESULT_DTYPE array of shape [...] (numpy either way), and with return_plain the best
+    hard decisions uint8 [..., 174] as well. count (optional, uint32 (nch,)): llr is the
+    (nch, max_cand, 174) layout ft8_sync writes; slots at or past count[ch] are not
+    decoded and give all-zero records."""
+    tl = _is_torch(llr)
+    if tl:
+        import torch
+
+        if not llr.is_cuda or not llr.is_contiguous() or llr.dtype != torch.float32:
+            raise ValueError("ldpc_decode_batch needs a contiguous float32 CUDA tensor")
+    else:
+        if not isinstance(llr, np.ndarray) or llr.dtype != np.float32:
+            raise ValueError("ldpc_decode_batch expects a float32 numpy array or torch CUDA tensor")
+        llr = np.ascontiguousarray(llr)
+    if llr.ndim < 1 or llr.shape[-1] != LDPC_N:
+        raise ValueError(f"expected LLRs of shape [..., 174], got {tuple(llr.shape)}")
+    shape = tuple(llr.shape[:-1])
+    n = int(np.prod(shape, dtype=np.int64))
+    mc = 0
+    if count is not None:
+        if llr.ndim != 3:
+            raise ValueError("count goes with LLRs of shape (nch, max_cand, 174)")
+        mc = int(shape[1])
+    proto, rl, mi = _PATTERNS[protocol], _rule(rule), int(max_iter)
+    if tl:
+        import torch
+
+        res = torch.empty(shape + (4,), dtype=torch.int32, device=llr.device)
+        plain = torch.empty(shape + (LDPC_N,), dtype=torch.uint8, device=llr.device) if return_plain else None
+        dcount = None
+        if count is not None:
+            dcount = count if _is_torch(count) else torch.from_numpy(np.ascontiguousarray(count, np.uint32).view(np.int32)).to(llr.device)
+            if dcount.numel() != shape[0] or not dcount.is_cuda or dcount.element_size() != 4:
+                raise ValueError("count: one 32-bit entry per channel")
+        _check(_L.orion_ldpc_decode_device(llr.data_ptr(), n, dcount.data_ptr() if dcount is not None else None, mc, proto,
+                                           rl, mi, res.data_ptr(), plain.data_ptr() if return_plain else None,
+                                           SyncEngine._stream(llr, stream)))
+        out = res.cpu().numpy().view(RESULT_DTYPE)[..., 0]
+        return (out, plain.cpu().numpy()) if return_plain else out
+    res = np.zeros(shape, RESULT_DTYPE)
+    plain = np.zeros(shape + (LDPC_N,), np.uint8) if return_plain else None
+    hcount = None
+    if count is not None:
+        hcount = np.ascontiguousarray(count, np.uint32)
+        if hcount.shape != (shape[0],):
+            raise ValueError("count: one entry per channel")
+    _check(_L.orion_ldpc_decode(llr.ctypes.data, n, hcount.ctypes.data if hcount is not None else None, mc, proto, rl, mi,
+                                res.ctypes.data, plain.ctypes.data if return_plain else None))
+    return (res, plain) if return_plain else res
+
+
+class _FtCodec:
+    """Ft8Codec / Ft4Codec (src/python/ft8.rs:94-160, 236-300): static encode, decode_hard
+    and decode_soft of one frame, on the library's host scalar decoder (one codeword is
+    not worth a launch). rule and max_iter are keyword extras; the defaults are the
+    reference's."""
+    _protocol = "ft8"
+    _tones = 58
+
+    @classmethod
+    def encode(cls, payload) -> np.ndarray:
+        payload = bytes(payload)
+        if len(payload) != 10:
+            raise ValueError("payload must be 10 bytes")
+        tones = np.zeros(cls._tones, np.uint8)
+        fn = _L.orion_ft8_encode if cls._protocol == "ft8" else _L.orion_ft4_encode
+        _check(fn(payload, tones.ctypes.data, None))
+        return tones
+
+    @classmethod
+    def frame_to_llr_hard(cls, tones) -> np.ndarray:
+        if not isinstance(tones, np.ndarray) or tones.dtype != np.uint8 or tones.shape != (cls._tones,):
+            raise ValueError(f"expected a uint8 array of {cls._tones} tones")
+        tones = np.ascontiguousarray(tones)
+        llr = np.zeros(LDPC_N, np.float32)
+        _check(_L.orion_ft_frame_to_llr_hard(_PATTERNS[cls._protocol], tones.ctypes.data, llr.ctypes.data))
+        return llr
+
+    @classmethod
+    def decode_hard(cls, tones, *, rule="reference", max_iter=20):
+        return cls.decode_soft(cls.frame_to_llr_hard(tones), rule=rule, max_iter=max_iter)
+
+    @classmethod
+    def decode_soft(cls, llr, *, rule="reference", max_iter=20):
+        res, _ = ldpc_decode_host(_llr174(llr), cls._protocol, rule, max_iter)
+        return res["payload"].tobytes() if res["status"] == 2 else None
+
+
+class Ft8Codec(_FtCodec):
+    _protocol, _tones = "ft8", 58
+
+
+class Ft4Codec(_FtCodec):
+    _protocol, _tones = "ft4", 87
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
