@@ -492,6 +492,67 @@ uint16_t orion_ft_crc14(const uint8_t* message, size_t num_bits);
  * (rows bit-packed MSB first). Any pointer may be NULL. */
 int orion_ldpc_tables(uint8_t* edges, uint16_t* row_start, uint8_t* bit_check, uint8_t* generator);
 
+/* ---- FT8 / FT4 modulators, slot synthesis and hard demodulators -------------------
+ * protocol: ORION_COSTAS_FT8 / ORION_COSTAS_FT4. A frame is 79 x 1920 = 151680 (FT8) or
+ * 105 x 576 = 60480 (FT4) cf32 samples; data tones are uint8 [58] (< 8) or [87] (< 4).
+ * The device modulator generates the closed form of the reference's own f32 tone steps
+ * (each step's exact angle as a Q0.64 turn count, phases as wrapping integer sums): it
+ * follows the reference's phasor recurrence to its rounding drift (1e-4 over a frame,
+ * DESIGN.md 3.3), not bit for bit; orion_ft_mod_host is the recurrence itself. The
+ * demodulator's energies and tones are the reference's bit for bit.
+ * Errors: ORION_E_ARG for an unknown protocol, a tone out of range, n_per_frame below the
+ * frame length or a signal's channel >= nch; ORION_E_NULL for a null pointer. */
+#define ORION_FT8_FRAME_LEN 151680
+#define ORION_FT4_FRAME_LEN 60480
+typedef struct orion_ft_mod orion_ft_mod;
+/* Ft8Mod::new / Ft4Mod::new, modulate/ft8.rs:55-62, ft4.rs:58-65. No device is touched here.
+ * rf_hz != 0: the phasors of a fresh Rotator(rf_hz, fs) over one frame (ft8.rs:150-153) are
+ * tabulated once, by the handle's first modulate call. */
+orion_ft_mod* orion_ft_mod_new(int protocol, float fs, float base_hz, float rf_hz, float gain);
+void orion_ft_mod_free(orion_ft_mod* h);
+/* Ft8Mod::modulate, ft8.rs:88-156 / Ft4Mod::modulate, ft4.rs:106-173, of nframes frames:
+ * tones [nframes][58 | 87] (host memory in both calls) -> iq [nframes][frame_len] cf32,
+ * host memory (synchronous) / device memory (launched on stream). */
+int orion_ft_mod_modulate(orion_ft_mod* h, const uint8_t* tones, size_t nframes, void* iq);
+int orion_ft_mod_modulate_device(orion_ft_mod* h, const uint8_t* tones, size_t nframes, void* iq, void* stream);
+/* The same frame by the reference's scalar recurrence (ft8.rs:94-153), bit for bit. Host
+ * only: no device is touched. iq [frame_len] cf32. */
+int orion_ft_mod_host(int protocol, float fs, float base_hz, float rf_hz, float gain, const uint8_t* tones, void* iq);
+/* build_symbol_sequence, ft8.rs:65-85 / ft4.rs:73-103: syms [79 | 105]. Host only. */
+int orion_ft_symbol_sequence(int protocol, const uint8_t* tones, uint8_t* syms);
+/* What the device modulator is built from (host only; any output may be NULL): w [8 | 4][2]
+ * the f32 step phasors (ft8.rs:98-101), step [8 | 4] their angles as Q0.64 turns, enter
+ * [79 | 105] the phase entering each symbol of the frame with these data tones. */
+int orion_ft_mod_tables(int protocol, float fs, float base_hz, const uint8_t* tones, float* w, uint64_t* step,
+                        uint64_t* enter);
+/* Slot synthesis: iq [nch][n_per_ch] cf32 = (accumulate ? iq : 0) + every signal's frame
+ * (what orion_ft_mod_modulate gives at fs, the signal's base_hz and gain, rf_hz 0) placed
+ * at its offset in its channel, clipped to the channel; the signals of a channel are summed
+ * in list order with plain f32 adds, so a call is bit-reproducible. signals [nsig] and tones
+ * [nsig][58 | 87] are host memory in both calls. */
+typedef struct {
+  uint32_t channel;
+  uint32_t pad;
+  int64_t offset; /* the channel sample at which the frame starts; may be negative */
+  float base_hz;
+  float gain;
+} orion_ft_signal;
+int orion_ft_synth(int protocol, float fs, const orion_ft_signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+                   size_t n_per_ch, int accumulate, void* iq);
+int orion_ft_synth_device(int protocol, float fs, const orion_ft_signal* signals, const uint8_t* tones, size_t nsig,
+                          size_t nch, size_t n_per_ch, int accumulate, void* iq, void* stream);
+/* Ft8Demod::demodulate, demodulate/ft8.rs:33-126 / Ft4Demod::demodulate, ft4.rs:35-74, of
+ * nframes rows of n_per_frame >= frame_len samples (the first frame_len of a row are
+ * read): tones [nframes][58 | 87]; energies (may be NULL) [nframes][79 | 105][8 | 4], every
+ * correlator energy of detect_tone (ft8.rs:74-126). nframes <= 65535 (ORION_E_ARG above).
+ * Host slices / device buffers. */
+int orion_ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                   uint8_t* tones, float* energies);
+int orion_ft_demod_device(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                          uint8_t* tones, float* energies, void* stream);
+/* The scalar demodulator the kernel is held to, one frame (iq: >= frame_len samples). Host only. */
+int orion_ft_demod_host(int protocol, float fs, float base_hz, const void* iq, uint8_t* tones, float* energies);
+
 #ifdef __cplusplus
 }
 #endif

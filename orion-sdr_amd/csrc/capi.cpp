@@ -20,6 +20,13 @@ struct orion_block {
 struct orion_sync {
   orion::Sync impl;
 };
+struct orion_ft_mod {
+  orion::FtMod impl;
+  orion_ft_mod(int protocol, float fs, float base_hz, float rf_hz, float gain) : impl(protocol, fs, base_hz, rf_hz, gain) {}
+};
+static_assert(sizeof(orion_ft_signal) == sizeof(orion::ftmod::Signal) && sizeof(orion_ft_signal) == 24 &&
+                  ORION_FT8_FRAME_LEN == 79 * 1920 && ORION_FT4_FRAME_LEN == 105 * 576,
+              "orion_ft_signal is ftmod.hpp's record");
 static_assert(sizeof(orion_candidate) == sizeof(orion::SyncCandidate) && sizeof(orion_candidate) == 12,
               "orion_candidate is the kernels' record");
 static_assert(sizeof(orion_ldpc_result) == sizeof(orion::ldpc::Result) && sizeof(orion_ldpc_result) == 16 &&
@@ -808,6 +815,106 @@ int orion_ldpc_tables(uint8_t* edges, uint16_t* row_start, uint8_t* bit_check, u
     if (row_start) std::memcpy(row_start, t.row_start, sizeof t.row_start);
     if (bit_check) std::memcpy(bit_check, t.bit_check, sizeof t.bit_check);
     if (generator) std::memcpy(generator, t.generator, sizeof t.generator);
+    return ORION_OK;
+  });
+}
+
+/* ---- FT8 / FT4 modulators, slot synthesis and hard demodulators (ftmod.hpp, k_ftmod.hip) ---- */
+orion_ft_mod* orion_ft_mod_new(int protocol, float fs, float base_hz, float rf_hz, float gain) {
+  try {
+    return new orion_ft_mod(protocol, fs, base_hz, rf_hz, gain);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_ft_mod_free(orion_ft_mod* h) { delete h; }
+int orion_ft_mod_modulate(orion_ft_mod* h, const uint8_t* tones, size_t nframes, void* iq) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (nframes && (!tones || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.modulate_host(tones, nframes, iq);
+    return ORION_OK;
+  });
+}
+int orion_ft_mod_modulate_device(orion_ft_mod* h, const uint8_t* tones, size_t nframes, void* iq, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (nframes && (!tones || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.modulate(tones, nframes, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ft_mod_host(int protocol, float fs, float base_hz, float rf_hz, float gain, const uint8_t* tones, void* iq) {
+  if (!tones || !iq) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ftmod::modulate_host(protocol, fs, base_hz, rf_hz, gain, tones, static_cast<float*>(iq));
+    return ORION_OK;
+  });
+}
+int orion_ft_symbol_sequence(int protocol, const uint8_t* tones, uint8_t* syms) {
+  if (!tones || !syms) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ftmod::symbol_sequence(protocol, tones, syms);
+    return ORION_OK;
+  });
+}
+int orion_ft_mod_tables(int protocol, float fs, float base_hz, const uint8_t* tones, float* w, uint64_t* step,
+                        uint64_t* enter) {
+  if (!tones && enter) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    float ww[2 * orion::ftmod::kMaxTones];
+    uint64_t q[orion::ftmod::kMaxTones];
+    const orion::ftmod::Proto& m = orion::ftmod::proto(protocol);
+    orion::ftmod::tone_steps(protocol, fs, base_hz, ww, q);
+    if (w) std::memcpy(w, ww, 2 * m.tones * sizeof(float));
+    if (step) std::memcpy(step, q, m.tones * sizeof(uint64_t));
+    if (enter) {
+      uint8_t syms[orion::ftmod::kMaxSyms];
+      orion::ftmod::symbol_sequence(protocol, tones, syms);
+      orion::ftmod::enter_phases(protocol, syms, q, enter);
+    }
+    return ORION_OK;
+  });
+}
+int orion_ft_synth(int protocol, float fs, const orion_ft_signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+                   size_t n_per_ch, int accumulate, void* iq) {
+  if ((nsig && (!signals || !tones)) || (nch && n_per_ch && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ft_synth_host(protocol, fs, reinterpret_cast<const orion::ftmod::Signal*>(signals), tones, nsig, nch, n_per_ch,
+                         accumulate != 0, iq);
+    return ORION_OK;
+  });
+}
+int orion_ft_synth_device(int protocol, float fs, const orion_ft_signal* signals, const uint8_t* tones, size_t nsig,
+                          size_t nch, size_t n_per_ch, int accumulate, void* iq, void* stream) {
+  if ((nsig && (!signals || !tones)) || (nch && n_per_ch && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ft_synth(protocol, fs, reinterpret_cast<const orion::ftmod::Signal*>(signals), tones, nsig, nch, n_per_ch,
+                    accumulate != 0, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                   uint8_t* tones, float* energies) {
+  if (nframes && (!iq || !tones)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ft_demod_host(protocol, fs, base_hz, iq, nframes, n_per_frame, tones, energies);
+    return ORION_OK;
+  });
+}
+int orion_ft_demod_device(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                          uint8_t* tones, float* energies, void* stream) {
+  if (nframes && (!iq || !tones)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ft_demod(protocol, fs, base_hz, iq, nframes, n_per_frame, tones, energies, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ft_demod_host(int protocol, float fs, float base_hz, const void* iq, uint8_t* tones, float* energies) {
+  if (!iq || !tones) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ftmod::demodulate_host(protocol, fs, base_hz, static_cast<const float*>(iq), tones, energies);
     return ORION_OK;
   });
 }

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "ftmod.hpp"
 #include "hip_common.hpp"
 
 namespace orion {
@@ -218,4 +219,19 @@ struct DecodePick {  // include/orion_sdr_amd.h orion_decode_pick
 };
 void launch_decode_pick(const SyncCandidate* cand_dev, const uint32_t* count_dev, const void* res_dev, int nch,
                         int max_cand, float base_hz, float spacing, DecodePick* pick_dev, hipStream_t s);
+
+// ------------------------- FT8 / FT4 modulators and hard demodulators (k_ftmod.hip) --
+// Slot synthesis: out [nch][n] cf32 = (accumulate ? out : 0) + the sum, in table order, of
+// every signal of the channel (rec_dev sorted by channel, rows_dev [nch + 1]: ftmod.hpp
+// SynthPlan), clipped to [0, n). rot_dev (optional, >= n phasors): the RF Rotator stage,
+// applied to each finished sample (Ft8Mod with rf_hz != 0: offset 0, n = the frame length).
+using FtSynthRecord = ftmod::SynthRecord;
+void launch_ft_synth(bool ft4, const FtSynthRecord* rec_dev, const uint32_t* rows_dev, f2* out_dev, int nch, long long n,
+                     bool accumulate, const f2* rot_dev, hipStream_t s);
+// Hard demodulator: x [nframes] rows of stride n >= the frame length (only the first
+// frame length of a row is read); steps: the tones' step phasors (host memory, [8 | 4][2],
+// ftmod.hpp demod_steps); tones_dev uint8 [nframes][58 | 87]; energies_dev (optional)
+// f32 [nframes][79 | 105][8 | 4].
+void launch_ft_demod(bool ft4, const f2* x_dev, int nframes, long long n, const float* steps, uint8_t* tones_dev,
+                     float* energies_dev, hipStream_t s);
 }  // namespace orion

@@ -2,6 +2,8 @@
 #include "sync_blocks.hpp"
 
 #include <cmath>
+#include <cstring>
+#include <mutex>
 #include <stdexcept>
 
 #include "ldpc.hpp"
@@ -214,6 +216,121 @@ void Sync::decode_host(int pattern, const void* iq, size_t nch, size_t n_per_ch,
   if (llr) ORION_HIP(hipMemcpy(llr, h_out_.as<void>(), lb, hipMemcpyDeviceToHost));
   ORION_HIP(hipMemcpy(results, rbase, rb, hipMemcpyDeviceToHost));
   ORION_HIP(hipMemcpy(pick, rbase + k_off, kb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+// ---- FT8 / FT4 modulators, slot synthesis and hard demodulators --------------------------
+FtSynth::~FtSynth() {
+  if (done_) (void)hipEventDestroy(done_);
+  if (pin_) (void)hipHostFree(pin_);
+}
+
+void FtSynth::run(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+                  size_t n, bool accumulate, void* iq, const f2* rot, hipStream_t s) {
+  ftmod::check_signals(protocol, signals, tones, nsig, nch);
+  if (n > (1ull << 36)) throw std::invalid_argument("synth: more than 2^36 samples per channel");
+  if (nch == 0 || n == 0) return;
+  const size_t rb = nsig * sizeof(ftmod::SynthRecord), bytes = rb + (nch + 1) * sizeof(uint32_t);
+  // the previous launch's copy out of the pinned plan and its reads of the device plan
+  if (!done_) ORION_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+  else ORION_HIP(hipEventSynchronize(done_));
+  if (bytes > pin_n_) {
+    if (pin_) ORION_HIP(hipHostFree(pin_));
+    pin_ = nullptr;
+    pin_n_ = 0;
+    ORION_HIP(hipHostMalloc(&pin_, bytes + bytes / 2, hipHostMallocDefault));
+    pin_n_ = bytes + bytes / 2;
+  }
+  tab_.resize(bytes);
+  char* h = static_cast<char*>(pin_);
+  ftmod::synth_plan_into(protocol, fs, signals, tones, nsig, nch, reinterpret_cast<ftmod::SynthRecord*>(h),
+                         reinterpret_cast<uint32_t*>(h + rb));
+  ORION_HIP(hipMemcpyAsync(tab_.as<void>(), pin_, bytes, hipMemcpyHostToDevice, s));
+  launch_ft_synth(protocol == ftmod::kFt4, tab_.as<FtSynthRecord>(), reinterpret_cast<const uint32_t*>(tab_.as<char>() + rb),
+                  static_cast<f2*>(iq), static_cast<int>(nch), static_cast<long long>(n), accumulate, rot, s);
+  ORION_HIP(hipEventRecord(done_, s));
+}
+
+FtMod::FtMod(int protocol, float fs, float base_hz, float rf_hz, float gain)
+    : protocol_(protocol), fs_(fs), base_hz_(base_hz), rf_hz_(rf_hz), gain_(gain) {
+  ftmod::proto(protocol);  // throws for an unknown protocol
+}
+
+void FtMod::modulate(const uint8_t* tones, size_t nframes, void* iq_dev, hipStream_t s) {
+  if (nframes > 0x7fffffffull) throw std::invalid_argument("modulate: more than 2^31 - 1 frames");
+  sig_.resize(nframes);
+  for (size_t f = 0; f < nframes; ++f) sig_[f] = ftmod::Signal{static_cast<uint32_t>(f), 0u, 0, base_hz_, gain_};
+  if (rf_hz_ != 0.0f && rot_.size() == 0) {  // the first device call: construction touches no device
+    std::vector<float> p(2 * frame_len());
+    ftmod::rotator_table(rf_hz_, fs_, frame_len(), p.data());
+    rot_.upload(p.data(), p.size() * sizeof(float), s);
+  }
+  synth_.run(protocol_, fs_, sig_.data(), tones, nframes, nframes, frame_len(), false, iq_dev,
+             rf_hz_ != 0.0f ? rot_.as<f2>() : nullptr, s);
+}
+
+void FtMod::modulate_host(const uint8_t* tones, size_t nframes, void* iq) {
+  const size_t ob = nframes * frame_len() * 8;
+  h_out_.resize(ob + 16);
+  modulate(tones, nframes, h_out_.as<void>(), nullptr);
+  if (ob) ORION_HIP(hipMemcpy(iq, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+namespace {
+std::mutex g_synth_mu;
+FtSynth& shared_synth() {
+  static FtSynth* p = new FtSynth;  // never destroyed: no HIP call at process exit
+  return *p;
+}
+}  // namespace
+
+void ft_synth(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+              size_t n, bool accumulate, void* iq_dev, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_synth_mu);
+  shared_synth().run(protocol, fs, signals, tones, nsig, nch, n, accumulate, iq_dev, nullptr, s);
+}
+
+void ft_synth_host(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+                   size_t n, bool accumulate, void* iq) {
+  ftmod::check_signals(protocol, signals, tones, nsig, nch);  // before any device call
+  if (n > (1ull << 36)) throw std::invalid_argument("synth: more than 2^36 samples per channel");
+  const size_t ob = nch * n * 8;
+  DevBuf d(ob + 16);
+  if (accumulate && ob) ORION_HIP(hipMemcpy(d.as<void>(), iq, ob, hipMemcpyHostToDevice));
+  ft_synth(protocol, fs, signals, tones, nsig, nch, n, accumulate, d.as<void>(), nullptr);
+  if (ob) ORION_HIP(hipMemcpy(iq, d.as<void>(), ob, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+void ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame, uint8_t* tones,
+              float* energies, hipStream_t s) {
+  const ftmod::Proto& m = ftmod::proto(protocol);
+  if (n_per_frame < static_cast<size_t>(m.frame_len()))
+    throw std::invalid_argument("demodulate: fewer samples per frame than a frame (FT8: 151680, FT4: 60480)");
+  if (nframes > kMaxCh || n_per_frame > (1ull << 40))
+    throw std::invalid_argument("demodulate: nframes <= 65535, n_per_frame <= 2^40");
+  float w[2 * ftmod::kMaxTones];
+  ftmod::demod_steps(protocol, fs, base_hz, w);
+  launch_ft_demod(protocol == ftmod::kFt4, static_cast<const f2*>(iq), static_cast<int>(nframes),
+                  static_cast<long long>(n_per_frame), w, tones, energies, s);
+}
+
+void ft_demod_host(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                   uint8_t* tones, float* energies) {
+  const ftmod::Proto& m = ftmod::proto(protocol);
+  if (n_per_frame < static_cast<size_t>(m.frame_len()))
+    throw std::invalid_argument("demodulate: fewer samples per frame than a frame (FT8: 151680, FT4: 60480)");
+  if (nframes > kMaxCh || n_per_frame > (1ull << 40))
+    throw std::invalid_argument("demodulate: nframes <= 65535, n_per_frame <= 2^40");
+  if (nframes == 0) return;
+  const size_t ib = nframes * n_per_frame * 8, tb = nframes * m.data, eb = energies ? nframes * m.total * m.tones * 4 : 0;
+  DevBuf d_iq(ib), d_t(tb + 16), d_e(eb + 16);
+  ORION_HIP(hipMemcpy(d_iq.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  ft_demod(protocol, fs, base_hz, d_iq.as<void>(), nframes, n_per_frame, d_t.as<uint8_t>(),
+           energies ? d_e.as<float>() : nullptr, nullptr);
+  ORION_HIP(hipMemcpy(tones, d_t.as<void>(), tb, hipMemcpyDeviceToHost));
+  if (eb) ORION_HIP(hipMemcpy(energies, d_e.as<void>(), eb, hipMemcpyDeviceToHost));
   ORION_HIP(hipDeviceSynchronize());
 }
 

@@ -83,4 +83,53 @@ void ldpc_decode(const float* llr, size_t n, const uint32_t* count, size_t max_c
 void ldpc_decode_host(const float* llr, size_t n, const uint32_t* count, size_t max_cand, int protocol, int rule,
                       size_t max_iter, void* results, uint8_t* plain);
 
+// ---- FT8 / FT4 modulators, slot synthesis and hard demodulators (ftmod.hpp, k_ftmod.hip) ----
+// The device copy of a synthesis plan and the launch over it. A call waits for the handle's
+// previous launch, builds the plan on the host in pinned memory (signals and tones are host
+// memory), and queues the copy and the launch on s: asynchronous once the buffers have grown
+// to the plan. iq is device memory [nch][n] cf32. rot: kernels.hpp launch_ft_synth.
+class FtSynth {
+ public:
+  ~FtSynth();
+  void run(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+           size_t n, bool accumulate, void* iq, const f2* rot, hipStream_t s);
+
+ private:
+  DevBuf tab_;
+  void* pin_ = nullptr;  // the plan as the host builds it (pinned: copied by DMA, no staging)
+  size_t pin_n_ = 0;
+  hipEvent_t done_ = nullptr;  // the last copy out of pin_ and launch over tab_
+};
+// Ft8Mod / Ft4Mod (modulate/ft8.rs:48-156, ft4.rs:51-173): nframes frames per call, tones
+// [nframes][58 | 87] (host) -> iq [nframes][frame_len] cf32. With rf_hz != 0 the Rotator's
+// phasors over one frame (a fresh Rotator per frame, ft8.rs:150-153: the reference's own,
+// from its recurrence on the host) are tabulated once, at the first device call: constructing
+// a modulator touches no device.
+class FtMod {
+ public:
+  FtMod(int protocol, float fs, float base_hz, float rf_hz, float gain);
+  size_t frame_len() const { return static_cast<size_t>(ftmod::proto(protocol_).frame_len()); }
+  void modulate(const uint8_t* tones, size_t nframes, void* iq_dev, hipStream_t s);
+  void modulate_host(const uint8_t* tones, size_t nframes, void* iq);
+
+ private:
+  int protocol_;
+  float fs_, base_hz_, rf_hz_, gain_;
+  DevBuf rot_, h_out_;
+  FtSynth synth_;
+  std::vector<ftmod::Signal> sig_;
+};
+// Slot synthesis on a shared plan buffer (one call at a time, process-wide).
+void ft_synth(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+              size_t n, bool accumulate, void* iq_dev, hipStream_t s);
+void ft_synth_host(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
+                   size_t n, bool accumulate, void* iq);
+// Ft8Demod / Ft4Demod (demodulate/ft8.rs:25-126, ft4.rs): iq [nframes] rows of n_per_frame
+// >= frame_len samples -> tones [nframes][58 | 87], energies (may be null) [nframes][79 |
+// 105][8 | 4]. Device pointers, asynchronous on s / host slices, synchronous.
+void ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame, uint8_t* tones,
+              float* energies, hipStream_t s);
+void ft_demod_host(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
+                   uint8_t* tones, float* energies);
+
 }  // namespace orion

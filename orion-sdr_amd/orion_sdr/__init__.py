@@ -34,6 +34,8 @@ __all__ = [
     "ft8_sync_batch", "ft4_sync_batch", "sync_geometry",
     "Ft8Codec", "Ft4Codec", "RESULT_DTYPE", "PICK_DTYPE", "LDPC_N", "ldpc_decode_batch", "ldpc_decode_host",
     "ldpc_tables", "ft_crc14", "ft8_decode", "ft4_decode", "ft8_decode_batch", "ft4_decode_batch",
+    "Ft8Mod", "Ft4Mod", "Ft8Demod", "Ft4Demod", "ft8_synth", "ft4_synth", "SIGNAL_DTYPE", "FT8_FRAME_LEN",
+    "FT4_FRAME_LEN",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -182,6 +184,16 @@ def _load():
         "orion_ldpc_decode_host": (i, [vp, i, i, sz, vp, vp]),
         "orion_ft_crc14": (C.c_uint16, [vp, sz]),
         "orion_ldpc_tables": (i, [vp, vp, vp, vp]),
+        "orion_ft_mod_new": (vp, [i, f, f, f, f]), "orion_ft_mod_free": (None, [vp]),
+        "orion_ft_mod_modulate": (i, [vp, vp, sz, vp]), "orion_ft_mod_modulate_device": (i, [vp, vp, sz, vp, vp]),
+        "orion_ft_mod_host": (i, [i, f, f, f, f, vp, vp]),
+        "orion_ft_symbol_sequence": (i, [i, vp, vp]),
+        "orion_ft_mod_tables": (i, [i, f, f, vp, vp, vp, vp]),
+        "orion_ft_synth": (i, [i, f, vp, vp, sz, sz, sz, i, vp]),
+        "orion_ft_synth_device": (i, [i, f, vp, vp, sz, sz, sz, i, vp, vp]),
+        "orion_ft_demod": (i, [i, f, f, vp, sz, sz, vp, vp]),
+        "orion_ft_demod_device": (i, [i, f, f, vp, sz, sz, vp, vp, vp]),
+        "orion_ft_demod_host": (i, [i, f, f, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1347,6 +1359,228 @@ class Ft8Codec(_FtCodec):
 
 class Ft4Codec(_FtCodec):
     _protocol, _tones = "ft4", 87
+
+
+# ---- FT8 / FT4 modulators, slot synthesis and hard demodulators ---------------------------
+FT8_FRAME_LEN = 79 * 1920
+FT4_FRAME_LEN = 105 * 576
+SIGNAL_DTYPE = np.dtype([("channel", np.uint32), ("pad", np.uint32), ("offset", np.int64), ("base_hz", np.float32),
+                         ("gain", np.float32)])
+_FT = {"ft8": (58, 79, 8, FT8_FRAME_LEN), "ft4": (87, 105, 4, FT4_FRAME_LEN)}  # data, total, tones, frame length
+
+
+def _ft_tones(tones, ndata, batched_ok=True):
+    """-> (C-contiguous uint8 array, nframes, batched); ValueError as the PyO3 classes."""
+    if not isinstance(tones, np.ndarray) or tones.dtype != np.uint8:
+        raise ValueError(f"expected a uint8 array of {ndata} tones")
+    if tones.ndim == 1 and tones.shape[0] == ndata:
+        return np.ascontiguousarray(tones), 1, False
+    if batched_ok and tones.ndim == 2 and tones.shape[1] == ndata:
+        return np.ascontiguousarray(tones), tones.shape[0], True
+    raise ValueError(f"expected {ndata} tones (or an (F, {ndata}) array), got shape {tuple(tones.shape)}")
+
+
+def _ft_arg(rc: int):
+    """A bad argument (a tone out of range, a channel >= nch) is a ValueError here."""
+    if rc == -3:
+        raise ValueError(f"orion_sdr: {_err()}")
+    _check(rc)
+
+
+class _FtMod:
+    """Ft8Mod / Ft4Mod (src/python/ft8.rs; modulate/ft8.rs:48-156, ft4.rs:51-173): data tones
+    -> one frame of complex64 IQ, on the GPU. The device generates the closed form of the
+    reference's own f32 tone steps, which follows the reference's phasor recurrence to its
+    rounding drift (about 1e-4 over a frame); modulate_host is the recurrence itself, bit
+    for bit, on the host."""
+    _protocol = "ft8"
+
+    def __init__(self, fs: float, base_hz: float, rf_hz: float = 0.0, gain: float = 1.0):
+        self._args = (float(fs), float(base_hz), float(rf_hz), float(gain))
+        h = _L.orion_ft_mod_new(_PATTERNS[self._protocol], *self._args)
+        if not h:
+            raise OrionError(f"orion_sdr: construction failed: {_err()}")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.orion_ft_mod_free(h)
+            self._h = None
+
+    def modulate(self, tones, device=False, stream=None):
+        """tones uint8 [58 | 87] -> complex64 [frame_len]; (F, 58 | 87) -> (F, frame_len). A new
+        array per call. device=True: a torch CUDA tensor, filled on torch's current stream."""
+        ndata, _, _, flen = _FT[self._protocol]
+        tones, nf, batched = _ft_tones(tones, ndata)
+        shape = (nf, flen) if batched else (flen,)
+        if device:
+            import torch
+
+            out = torch.empty(shape, dtype=torch.complex64, device="cuda")
+            _ft_arg(_L.orion_ft_mod_modulate_device(self._h, tones.ctypes.data, nf, out.data_ptr(),
+                                                    SyncEngine._stream(out, stream)))
+            return out
+        out = np.empty(shape, np.complex64)
+        _ft_arg(_L.orion_ft_mod_modulate(self._h, tones.ctypes.data, nf, out.ctypes.data))
+        return out
+
+    def modulate_host(self, tones) -> np.ndarray:
+        """The reference's own samples (its scalar recurrence, on the host)."""
+        ndata, _, _, flen = _FT[self._protocol]
+        tones, _, _ = _ft_tones(tones, ndata, batched_ok=False)
+        out = np.empty(flen, np.complex64)
+        _ft_arg(_L.orion_ft_mod_host(_PATTERNS[self._protocol], *self._args, tones.ctypes.data, out.ctypes.data))
+        return out
+
+    @classmethod
+    def symbol_sequence(cls, tones) -> np.ndarray:
+        """build_symbol_sequence: the 79 | 105 frame symbols, sync (and FT4 ramp) symbols included."""
+        ndata, total, _, _ = _FT[cls._protocol]
+        tones, _, _ = _ft_tones(tones, ndata, batched_ok=False)
+        syms = np.zeros(total, np.uint8)
+        _ft_arg(_L.orion_ft_symbol_sequence(_PATTERNS[cls._protocol], tones.ctypes.data, syms.ctypes.data))
+        return syms
+
+    def tables(self, tones=None):
+        """(w complex64 [8 | 4], step uint64 [8 | 4], enter uint64 [79 | 105] or None): the f32
+        step phasors, their angles as Q0.64 turns and the phase entering each symbol."""
+        ndata, total, nt, _ = _FT[self._protocol]
+        w = np.zeros(nt, np.complex64)
+        step = np.zeros(nt, np.uint64)
+        enter = None
+        tp = None
+        if tones is not None:
+            tones, _, _ = _ft_tones(tones, ndata, batched_ok=False)
+            enter = np.zeros(total, np.uint64)
+            tp = tones.ctypes.data
+        _ft_arg(_L.orion_ft_mod_tables(_PATTERNS[self._protocol], self._args[0], self._args[1], tp, w.ctypes.data,
+                                       step.ctypes.data, enter.ctypes.data if enter is not None else None))
+        return w, step, enter
+
+
+class Ft8Mod(_FtMod):
+    _protocol = "ft8"
+
+
+class Ft4Mod(_FtMod):
+    _protocol = "ft4"
+
+
+class _FtDemod:
+    """Ft8Demod / Ft4Demod (src/python/ft8.rs; demodulate/ft8.rs:25-126, ft4.rs): the argmax
+    tone of every symbol's correlator energies, sync positions dropped; the reference's
+    arithmetic bit for bit. IQ: complex64, 1-D or (F, n) with n >= a frame (only the first
+    frame length of a row is read); a numpy array or a torch CUDA tensor."""
+    _protocol = "ft8"
+
+    def __init__(self, fs: float, base_hz: float):
+        self._args = (float(fs), float(base_hz))
+
+    def _run(self, iq, want_energies, stream=None):
+        ndata, total, nt, flen = _FT[self._protocol]
+        try:
+            iq, nf, n, batched = SyncEngine._iq(iq)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+        if n < flen:
+            raise ValueError(f"expected at least {flen} samples per frame, got {n}")
+        proto = _PATTERNS[self._protocol]
+        tshape = (nf, ndata) if batched else (ndata,)
+        eshape = (nf, total, nt) if batched else (total, nt)
+        if _is_torch(iq):
+            import torch
+
+            tones = torch.empty(tshape, dtype=torch.uint8, device=iq.device)
+            en = torch.empty(eshape, dtype=torch.float32, device=iq.device) if want_energies else None
+            _ft_arg(_L.orion_ft_demod_device(proto, *self._args, iq.data_ptr(), nf, n, tones.data_ptr(),
+                                             en.data_ptr() if want_energies else None, SyncEngine._stream(iq, stream)))
+            return tones.cpu().numpy(), (en.cpu().numpy() if want_energies else None)
+        tones = np.zeros(tshape, np.uint8)
+        en = np.zeros(eshape, np.float32) if want_energies else None
+        _ft_arg(_L.orion_ft_demod(proto, *self._args, iq.ctypes.data, nf, n, tones.ctypes.data,
+                                  en.ctypes.data if want_energies else None))
+        return tones, en
+
+    def demodulate(self, iq) -> np.ndarray:
+        """-> uint8 [58 | 87], or (F, 58 | 87) for (F, n) input (numpy either way)."""
+        return self._run(iq, False)[0]
+
+    def energies(self, iq) -> np.ndarray:
+        """Every correlator energy: float32 (79 | 105, 8 | 4), with a leading F axis for (F, n)."""
+        return self._run(iq, True)[1]
+
+    def demodulate_host(self, iq, return_energies=False):
+        """The library's scalar demodulator (host only; what the kernel is held to), one frame."""
+        ndata, total, nt, flen = _FT[self._protocol]
+        if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != 1 or len(iq) < flen:
+            raise ValueError(f"expected a 1-D complex64 array of at least {flen} samples")
+        iq = np.ascontiguousarray(iq)
+        tones = np.zeros(ndata, np.uint8)
+        en = np.zeros((total, nt), np.float32)
+        _ft_arg(_L.orion_ft_demod_host(_PATTERNS[self._protocol], *self._args, iq.ctypes.data, tones.ctypes.data,
+                                       en.ctypes.data))
+        return (tones, en) if return_energies else tones
+
+
+class Ft8Demod(_FtDemod):
+    _protocol = "ft8"
+
+
+class Ft4Demod(_FtDemod):
+    _protocol = "ft4"
+
+
+def _ft_synth(protocol, signals, tones, n, nch, fs, out, accumulate, device, stream):
+    ndata = _FT[protocol][0]
+    if not isinstance(signals, np.ndarray) or signals.dtype != SIGNAL_DTYPE or signals.ndim != 1:
+        raise ValueError("signals: a 1-D array of SIGNAL_DTYPE")
+    signals = np.ascontiguousarray(signals)
+    nsig = len(signals)
+    if not isinstance(tones, np.ndarray) or tones.dtype != np.uint8 or tones.shape != (nsig, ndata):
+        raise ValueError(f"tones: a uint8 array of shape ({nsig}, {ndata})")
+    tones = np.ascontiguousarray(tones)
+    n, nch = int(n), int(nch)
+    if n < 0 or nch < 1:
+        raise ValueError("n >= 0 and nch >= 1")
+    proto = _PATTERNS[protocol]
+    if out is not None:
+        if tuple(out.shape) != (nch, n):
+            raise ValueError(f"out: expected shape ({nch}, {n}), got {tuple(out.shape)}")
+    elif accumulate:
+        raise ValueError("accumulate needs out")
+    if (out is not None and _is_torch(out)) or (out is None and device):
+        import torch
+
+        if out is None:
+            out = torch.empty((nch, n), dtype=torch.complex64, device="cuda")
+        elif not out.is_cuda or not out.is_contiguous() or out.dtype != torch.complex64:
+            raise ValueError("out: a contiguous complex64 CUDA tensor")
+        _ft_arg(_L.orion_ft_synth_device(proto, float(fs), signals.ctypes.data, tones.ctypes.data, nsig, nch, n,
+                                         1 if accumulate else 0, out.data_ptr(), SyncEngine._stream(out, stream)))
+        return out
+    if out is None:
+        out = np.empty((nch, n), np.complex64)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.complex64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("out: a C-contiguous complex64 array")
+    _ft_arg(_L.orion_ft_synth(proto, float(fs), signals.ctypes.data, tones.ctypes.data, nsig, nch, n,
+                              1 if accumulate else 0, out.ctypes.data))
+    return out
+
+
+def ft8_synth(signals, tones, n, nch=1, fs=12000.0, out=None, accumulate=False, device=False, stream=None):
+    """Slot synthesis on the GPU: (nch, n) complex64 holding every signal's FT8 frame (as
+    Ft8Mod(fs, base_hz, 0, gain).modulate gives it) at its offset in its channel, clipped to
+    the channel, a channel's signals summed in list order (bit-reproducible). signals: a
+    SIGNAL_DTYPE array (channel, offset, base_hz, gain); tones uint8 (nsig, 58). out: a numpy
+    array or torch CUDA tensor to fill (accumulate: to add to); device=True: a new CUDA
+    tensor, filled on torch's current stream."""
+    return _ft_synth("ft8", signals, tones, n, nch, fs, out, accumulate, device, stream)
+
+
+def ft4_synth(signals, tones, n, nch=1, fs=12000.0, out=None, accumulate=False, device=False, stream=None):
+    """ft8_synth for FT4 frames: tones uint8 (nsig, 87)."""
+    return _ft_synth("ft4", signals, tones, n, nch, fs, out, accumulate, device, stream)
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
