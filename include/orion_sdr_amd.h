@@ -553,6 +553,250 @@ int orion_ft_demod_device(int protocol, float fs, float base_hz, const void* iq,
 /* The scalar demodulator the kernel is held to, one frame (iq: >= frame_len samples). Host only. */
 int orion_ft_demod_host(int protocol, float fs, float base_hz, const void* iq, uint8_t* tones, float* energies);
 
+/* ---- PSK31 channel code: Varicode and QPSK31's rate 1/2, K = 5 code (src/codec) ---
+ * Bits are uint8, one per byte, 0 or 1 (only bit 0 of an input byte is read). Everything
+ * in this section but orion_psk31_viterbi and orion_psk31_viterbi_device is host only: no
+ * device is touched. Errors: ORION_E_NULL for a null pointer or handle, ORION_E_ARG for a
+ * count above its limit or an output capacity below what the call produces. */
+#define ORION_VARICODE_MAX_BITS 10    /* codec/varicode.rs:20 */
+#define ORION_PSK31_TRACEBACK_DEPTH 32 /* codec/psk31.rs:267 */
+/* The tables as the library holds them (any pointer may be NULL): the Varicode alphabet
+ * (varicode.rs:27-156) as codewords [128], MSB first, and their lengths [128]; DQPSK_EXP
+ * (psk31.rs:80-85) as dqpsk_exp [4][2]. */
+int orion_psk31_tables(uint16_t* varicode_bits, uint8_t* varicode_len, float* dqpsk_exp);
+/* varicode_encode, varicode.rs:163-169 (a byte >= 128 gives the NUL entry), and
+ * varicode_decode, varicode.rs:176-183: the byte, or -1 for a codeword not in the table. */
+int orion_varicode_encode(uint8_t byte, uint16_t* bits, uint8_t* len);
+int orion_varicode_decode(uint16_t bits, uint8_t len);
+/* VaricodeEncoder, varicode.rs:192-267. push_preamble leaves the next byte without a "00"
+ * gap of its own (varicode.rs:216-223). pending: the bits queued; drain copies and removes
+ * them all (cap below pending: ORION_E_ARG, nothing removed). */
+typedef struct orion_varicode_encoder orion_varicode_encoder;
+orion_varicode_encoder* orion_varicode_encoder_new(void);
+void orion_varicode_encoder_free(orion_varicode_encoder* e);
+int orion_varicode_encoder_push_preamble(orion_varicode_encoder* e, size_t n_bits);
+int orion_varicode_encoder_push_byte(orion_varicode_encoder* e, uint8_t byte);
+int orion_varicode_encoder_push_postamble(orion_varicode_encoder* e, size_t n_bits);
+size_t orion_varicode_encoder_pending(const orion_varicode_encoder* e);
+int orion_varicode_encoder_drain(orion_varicode_encoder* e, uint8_t* bits, size_t cap, size_t* n_bits);
+/* VaricodeDecoder, varicode.rs:277-320 (its length counter stops at ORION_VARICODE_MAX_BITS
+ * + 1). push_bits feeds n bits; pending: the characters decoded and not yet popped;
+ * pop_bytes copies and removes them all (cap below pending: ORION_E_ARG, nothing removed). */
+typedef struct orion_varicode_decoder orion_varicode_decoder;
+orion_varicode_decoder* orion_varicode_decoder_new(void);
+void orion_varicode_decoder_free(orion_varicode_decoder* d);
+int orion_varicode_decoder_push_bits(orion_varicode_decoder* d, const uint8_t* bits, size_t n);
+size_t orion_varicode_decoder_pending(const orion_varicode_decoder* d);
+int orion_varicode_decoder_pop_bytes(orion_varicode_decoder* d, uint8_t* bytes, size_t cap, size_t* n_bytes);
+/* conv_encode, psk31.rs:45-55: bits [n] -> coded [2 n], (g0, g1) per bit, G0 = 25, G1 = 23
+ * octal, from a zero register. */
+int orion_conv_encode(const uint8_t* bits, size_t n, uint8_t* coded);
+/* viterbi_decode, psk31.rs:95-160, of nstreams streams in one launch: soft [nstreams][2 *
+ * n_syms] f32 (re, im of each differential symbol) -> bits [nstreams][n_syms]. Sixteen lanes
+ * per stream, four streams per wave; the bits are those of orion_psk31_viterbi_host for every
+ * input (the start metric f32::MAX / 2, the skip of predecessors at it, strict < on the
+ * second predecessor, the first minimum at the end). NaN input is outside the contract; it
+ * neither faults nor hangs. nstreams <= 2^31 - 4, n_syms <= 2^31 - 1 (ORION_E_ARG above).
+ * Host slices (uploaded, one launch, downloaded; synchronous) or device buffers on a stream;
+ * the device call needs work, device memory of at least orion_psk31_viterbi_work_bytes
+ * (nstreams, n_syms) bytes (4 bytes per stream, rounded up to 4 streams, and symbol), which
+ * it may overwrite wholly. */
+int orion_psk31_viterbi(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits);
+int orion_psk31_viterbi_device(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits, void* work,
+                               size_t work_bytes, void* stream);
+size_t orion_psk31_viterbi_work_bytes(size_t nstreams, size_t n_syms);
+/* The scalar decoder the kernel is held to, one stream: soft [2 n_syms] -> bits [n_syms];
+ * and viterbi_decode_hard, psk31.rs:384-396: coded [2 n_syms] bits -> bits [n_syms]. */
+int orion_psk31_viterbi_host(const float* soft, size_t n_syms, uint8_t* bits);
+int orion_psk31_viterbi_hard_host(const uint8_t* coded, size_t n_syms, uint8_t* bits);
+/* StreamingViterbi, psk31.rs:257-377, on DQPSK_EXP: feed takes n_syms symbols (soft [2
+ * n_syms]) and writes the bits that come out, none for the first 32 symbols of a decoder
+ * and one per symbol after (bits holds n_syms); flush feeds 32 (0, 0) symbols (bits holds
+ * 32). *n_bits: how many were written. */
+typedef struct orion_psk31_streaming_viterbi orion_psk31_streaming_viterbi;
+orion_psk31_streaming_viterbi* orion_psk31_streaming_viterbi_new(void);
+void orion_psk31_streaming_viterbi_free(orion_psk31_streaming_viterbi* v);
+int orion_psk31_streaming_viterbi_feed(orion_psk31_streaming_viterbi* v, const float* soft, size_t n_syms,
+                                       uint8_t* bits, size_t* n_bits);
+int orion_psk31_streaming_viterbi_flush(orion_psk31_streaming_viterbi* v, uint8_t* bits, size_t* n_bits);
+
+/* ---- PSK31 modulators and demodulators (src/modulate/psk31.rs, src/demodulate/psk31.rs)
+ * 31.25 baud; a symbol is round(fs / 31.25) samples (psk31_sps, modulate/psk31.rs:42-44: 256
+ * at 8 kHz, 384 at 12 kHz; 0 or above 2^24: ORION_E_ARG). mode: ORION_PSK31_BPSK /
+ * ORION_PSK31_QPSK, another value is ORION_E_ARG. The scalar modulators and demodulators
+ * of this section run on the host, in the reference's f32 operation order (glibc sinf /
+ * cosf); the demodulator bank is the device path. */
+#define ORION_PSK31_BPSK 0
+#define ORION_PSK31_QPSK 1
+size_t orion_psk31_sps(float fs);
+/* The bits modulate_text sends (modulate/psk31.rs:146-159): preamble zeros, the Varicode of
+ * the bytes, "00" and postamble ones. cap below the count: ORION_E_ARG with *n_bits set to
+ * the count (bits may then be NULL: a size query). */
+int orion_psk31_text_bits(const uint8_t* text, size_t n, size_t preamble_bits, size_t postamble_bits, uint8_t* bits,
+                          size_t cap, size_t* n_bits);
+/* Bpsk31Mod, modulate/psk31.rs:110-216 (bit 0 flips the phase: only a zero byte is a 0), and
+ * Qpsk31Mod, :248-362 (the coder's register and the phasor are kept between calls; the
+ * phasor is the f32 pair the reference's products give, -0.0 included). Host only.
+ * modulate_bits: bits [n] -> iq [n * sps] cf32; with rf_hz != 0 a fresh Rotator runs over
+ * each call's output (:186-189). */
+typedef struct orion_psk31_mod orion_psk31_mod;
+orion_psk31_mod* orion_psk31_mod_new(int mode, float fs, float rf_hz, float gain);
+void orion_psk31_mod_free(orion_psk31_mod* m);
+int orion_psk31_mod_set_gain(orion_psk31_mod* m, float gain);
+int orion_psk31_mod_reset(orion_psk31_mod* m);
+int orion_psk31_mod_modulate_bits(orion_psk31_mod* m, const uint8_t* bits, size_t n, void* iq);
+/* The device modulator (k_psk31_mod, one lane per output sample): the symbol phasors are
+ * built on the host with the reference's arithmetic, the Hann cross-fade and the RF stage
+ * (the phasors of a fresh Rotator, tabulated from the reference's own recurrence and kept on
+ * the device) run in the kernel, operation for operation as the host modulator: the output
+ * equals orion_psk31_mod_modulate_bits byte for byte at any length. bits are host memory.
+ * _bits_device: one stream from the handle's state, which advances; iq [n * sps] device.
+ * _batch / _batch_device: nstreams independent streams bits [nstreams][n], each from a fresh
+ * modulator of the handle's parameters (the handle's state is not touched) -> iq [nstreams]
+ * [n * sps], host memory (synchronous) / device memory. nstreams <= 2^24. */
+int orion_psk31_mod_modulate_bits_device(orion_psk31_mod* m, const uint8_t* bits, size_t n, void* iq, void* stream);
+int orion_psk31_mod_modulate_batch(orion_psk31_mod* m, const uint8_t* bits, size_t nstreams, size_t n, void* iq);
+int orion_psk31_mod_modulate_batch_device(orion_psk31_mod* m, const uint8_t* bits, size_t nstreams, size_t n, void* iq,
+                                          void* stream);
+/* Band synthesis (k_psk31_synth; no reference counterpart): iq [nch][n_per_ch] cf32 =
+ * (accumulate ? iq : 0) + every signal, what a fresh Bpsk31Mod / Qpsk31Mod(fs, rf_hz, gain)
+ * gives for its bits, placed at its offset in its channel and clipped to the channel; the
+ * signals of a channel are summed in list order with plain f32 adds, so a call is
+ * bit-reproducible. The RF stage is the closed form of the Rotator's f32 step (its angle as
+ * a Q0.64 turn count, orion_psk31_rotator_q64): it follows the reference's recurrence to its
+ * rounding drift, 2 d0 + 2e-6 per unit gain with d0 the distance between the recurrence and
+ * that closed form, not bit for bit; with rf_hz == 0 a signal is the host
+ * modulator's bytes. signals [nsig] and bits (signal k's n_bits bits follow signal k - 1's)
+ * are host memory in both calls. ORION_E_ARG: channel >= nch, an unknown mode, nsig > 2^24. */
+typedef struct {
+  uint32_t channel;
+  uint32_t mode;   /* ORION_PSK31_BPSK / ORION_PSK31_QPSK */
+  int64_t offset;  /* the channel sample at which the signal starts; may be negative */
+  float rf_hz;
+  float gain;
+  uint64_t n_bits;
+} orion_psk31_signal;
+int orion_psk31_synth(float fs, const orion_psk31_signal* signals, const uint8_t* bits, size_t nsig, size_t nch,
+                      size_t n_per_ch, int accumulate, void* iq);
+int orion_psk31_synth_device(float fs, const orion_psk31_signal* signals, const uint8_t* bits, size_t nsig, size_t nch,
+                             size_t n_per_ch, int accumulate, void* iq, void* stream);
+/* The angle of Rotator(freq_hz, fs)'s f32 step phasor as a Q0.64 fraction of a turn. Host only. */
+uint64_t orion_psk31_rotator_q64(float freq_hz, float fs);
+/* Block::process, :199-215: min(n_bits, out_cap / sps) bits are read. */
+int orion_psk31_mod_process(orion_psk31_mod* m, const uint8_t* bits, size_t n_bits, void* iq, size_t out_cap,
+                            orion_work_report* report);
+/* Bpsk31Demod, demodulate/psk31.rs:83-220 (offset: new_with_offset, :104-130), and
+ * Qpsk31Demod, :271-397, on the host: the scalar demodulators the bank is held to. BPSK
+ * writes one soft value per symbol and stops when out_written == out_cap; QPSK writes (re,
+ * im) of the differential product and stops when out_written + 1 >= out_cap. */
+typedef struct orion_psk31_demod orion_psk31_demod;
+orion_psk31_demod* orion_psk31_demod_new(int mode, float fs, float rf_hz, float gain, size_t offset);
+void orion_psk31_demod_free(orion_psk31_demod* d);
+int orion_psk31_demod_set_gain(orion_psk31_demod* d, float gain);
+int orion_psk31_demod_reset(orion_psk31_demod* d);
+int orion_psk31_demod_process(orion_psk31_demod* d, const void* iq, size_t n, float* soft, size_t out_cap,
+                              orion_work_report* report);
+/* Bpsk31Decider, demodulate/psk31.rs:236-261: bits[i] = soft[i] >= 0. Host only. */
+int orion_bpsk31_decide(const float* soft, size_t n, uint8_t* bits);
+/* What a bank stream (below) or a sync candidate read and wrote in a call. */
+typedef struct {
+  uint64_t in_read;
+  uint64_t out_written;
+} orion_psk31_report;
+/* The carrier search of psk31_sync (sync/psk31_sync.rs:82-203) on the host, over log
+ * waterfalls given to it: wf [nch][num_syms][num_bins] as orion_waterfall_compute writes it
+ * with ORION_WF_LOG, one bin per 31.25 Hz. Per bin the median over time, per channel the
+ * median of those (median_f32: even counts average the two middle values); ln_margin =
+ * peak_margin_db * LN_2 / 3; a symbol is a peak when (e > bin_median + ln_margin ||
+ * bin_median > noise_floor + ln_margin) && e >= e_left && e >= e_right; runs of at least
+ * max(min_carrier_syms, 1) peaks count, a run that reaches the end of the buffer included;
+ * score = run_energy_sum / run_len. cand [nch][max_cand] (time_sym the run's first symbol;
+ * unused slots zeroed), count [nch]: the max_cand best runs per channel, score descending.
+ * The reference sorts with sort_unstable_by on the score alone, which leaves the order of
+ * runs of equal score open; here it is defined: equal scores are ordered by freq_bin, then
+ * time_sym, both ascending, one of the orders the reference may produce.
+ * max_cand == 0 is ORION_E_ARG, as for the FT entries; nch * num_syms * num_bins < 2^31. */
+int orion_psk31_find_carriers_host(const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                                   size_t min_carrier_syms, float peak_margin_db, size_t max_cand,
+                                   orion_candidate* cand, uint32_t* count);
+/* The same search on the device, on the orion_sync handle (which owns its scratch): four
+ * small kernels (medians over time by exact selection, each channel's noise floor, one
+ * serial scan per channel and bin with the f32 run sum in symbol order, a merge of the bins'
+ * lists); no list is appended to in arrival order, so the output does not depend on
+ * scheduling and equals orion_psk31_find_carriers_host on the same waterfall, order and
+ * scores included. Host slices (uploaded, run, downloaded; synchronous) / device buffers on
+ * a stream. Limits (ORION_E_ARG): those of the host entry, nch * num_bins * max_cand <= 2^26,
+ * num_bins * max_cand <= 2^22. */
+int orion_psk31_find_carriers(orion_sync* h, const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                              size_t min_carrier_syms, float peak_margin_db, size_t max_cand, orion_candidate* cand,
+                              uint32_t* count);
+int orion_psk31_find_carriers_device(orion_sync* h, const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                                     size_t min_carrier_syms, float peak_margin_db, size_t max_cand,
+                                     orion_candidate* cand, uint32_t* count, void* stream);
+/* psk31_sync, sync/psk31_sync.rs:50-239, batched over channels, all on the device with no
+ * trip to the host between its stages: iq [nch][n_per_ch] cf32 -> the waterfall (one bin per
+ * 31.25 Hz from base_hz, round(fs / 31.25) samples per symbol, n_per_ch / sps symbols) -> the
+ * search above -> for every kept candidate a BPSK31 stream as record_candidate starts it
+ * (:209-239: carrier base_hz + f32(freq_bin) * 31.25, from sample time_sym * sps, gain 1,
+ * capacity n_bits + 2), written as bank records on the device and demodulated by one launch
+ * of the demodulator bank. cand [nch][max_cand], count [nch]; soft [nch][max_cand][n_bits +
+ * 2] f32 (zeroed first), reports [nch][max_cand] {in_read, out_written}: the reference keeps
+ * the first min(out_written, n_bits) values of a candidate. A buffer under one symbol gives
+ * count 0. The soft values follow the host demodulator's as the bank's do.
+ * Limits as above, n_bits <= 2^30 - 2, nch * max_cand * (n_bits + 2) <= 2^32. */
+int orion_psk31_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand,
+                     orion_candidate* cand, uint32_t* count, float* soft, orion_psk31_report* reports);
+int orion_psk31_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand,
+                            orion_candidate* cand, uint32_t* count, float* soft, orion_psk31_report* reports,
+                            void* stream);
+/* psk31_sync's bin count, psk31_sync.rs:70-71: ceil(max(max_hz - base_hz, 0) / 31.25) + 1;
+ * 0 when the range is above 2^24 bins. */
+size_t orion_psk31_sync_num_bins(float base_hz, float max_hz);
+/* The demodulator bank: nstreams independent demodulators over nch channels, all advanced
+ * by one kernel launch per call, one lane per stream (a stream is one serial chain in time:
+ * every sample's correction uses the previous symbol's decision-feedback sum). Each call
+ * takes iq [nch][n] cf32, the next n samples of every channel. A stream reads its channel
+ * from the channel sample `start` on (counted from the bank's first call or last reset),
+ * with the symbol clock of new_with_offset(.., offset), and writes at most out_cap soft
+ * values per call (the reference's output.len(): BPSK stops at out_cap, QPSK when fewer
+ * than two slots are left); a stream that stops early has in_read < the samples offered,
+ * and the next call still brings every stream its channel's next samples.
+ * soft [nstreams][out_stride] f32 with out_stride >= every out_cap; bits (may be NULL) the
+ * same shape: for a BPSK31 stream bits = soft >= 0 (Bpsk31Decider); the rows of QPSK31
+ * streams are not written (a pair's quadrature component is noise about zero, and QPSK31's
+ * decisions are the Viterbi decoder's: orion_psk31_viterbi on the soft pairs); reports
+ * [nstreams] {in_read, out_written} of this call.
+ * State is carried between calls, so chunked calls give one call's bytes. Against the host
+ * demodulator the soft values agree to a few ulp, not bit for bit: phase_acc's sine and
+ * cosine are glibc's there and a correctly-rounded-but-for-near-ties pair here (DESIGN.md
+ * 3.3). Limits (ORION_E_ARG): nch <= 65535, nstreams <= 2^24, out_cap <= 2^30, channel < nch. */
+typedef struct {
+  uint32_t mode;    /* ORION_PSK31_BPSK / ORION_PSK31_QPSK */
+  uint32_t channel;
+  float rf_hz;      /* the carrier to mix down from; 0: no rotator at all */
+  float gain;
+  uint64_t start;   /* first channel sample the stream reads */
+  uint32_t offset;  /* new_with_offset's offset */
+  uint32_t out_cap; /* soft values per call */
+} orion_psk31_stream;
+typedef struct orion_psk31_demod_bank orion_psk31_demod_bank;
+/* No device is touched here: the bank's tables are uploaded by its first process call. */
+orion_psk31_demod_bank* orion_psk31_demod_bank_new(float fs, const orion_psk31_stream* streams, size_t nstreams,
+                                                   size_t nch);
+void orion_psk31_demod_bank_free(orion_psk31_demod_bank* b);
+/* Host slices (synchronous) / device buffers (launched on stream). */
+int orion_psk31_demod_bank_process(orion_psk31_demod_bank* b, const void* iq, size_t nch, size_t n, float* soft,
+                                   size_t out_stride, uint8_t* bits, orion_psk31_report* reports);
+int orion_psk31_demod_bank_process_device(orion_psk31_demod_bank* b, const void* iq, size_t nch, size_t n, float* soft,
+                                          size_t out_stride, uint8_t* bits, orion_psk31_report* reports, void* stream);
+/* Every stream back to its initial state and the sample count to 0 (waits for the device). */
+int orion_psk31_demod_bank_reset(orion_psk31_demod_bank* b);
+/* set_gain (demodulate/psk31.rs:132-134) of stream `index` of the list the bank was built
+ * from; takes effect with the next call (which waits for the device once). */
+int orion_psk31_demod_bank_set_gain(orion_psk31_demod_bank* b, size_t index, float gain);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@
 #include "blocks.hpp"
 #include "ldpc.hpp"
 #include "osc.hpp"
+#include "psk31.hpp"
+#include "psk31_blocks.hpp"
 #include "scan_blocks.hpp"
 #include "sync_blocks.hpp"
 
@@ -19,11 +21,44 @@ struct orion_block {
 };
 struct orion_sync {
   orion::Sync impl;
+  orion::Psk31Sync psk;
 };
 struct orion_ft_mod {
   orion::FtMod impl;
   orion_ft_mod(int protocol, float fs, float base_hz, float rf_hz, float gain) : impl(protocol, fs, base_hz, rf_hz, gain) {}
 };
+struct orion_varicode_encoder {
+  orion::psk31::VaricodeEncoder impl;
+};
+struct orion_varicode_decoder {
+  orion::psk31::VaricodeDecoder impl;
+};
+struct orion_psk31_streaming_viterbi {
+  orion::psk31::StreamingViterbi impl;
+};
+struct orion_psk31_mod {
+  orion::Psk31ModDev dev;
+  orion::psk31::Mod& impl;
+  orion_psk31_mod(int mode, float fs, float rf_hz, float gain) : dev(mode, fs, rf_hz, gain), impl(dev.host()) {}
+};
+struct orion_psk31_demod {
+  orion::psk31::Demod impl;
+  orion_psk31_demod(int mode, float fs, float rf_hz, float gain, size_t offset) : impl(mode, fs, rf_hz, gain, offset) {}
+};
+struct orion_psk31_demod_bank {
+  orion::Psk31DemodBank impl;
+  orion_psk31_demod_bank(float fs, const orion::psk31::Stream* streams, size_t nstreams, size_t nch)
+      : impl(fs, streams, nstreams, nch) {}
+};
+static_assert(sizeof(orion_psk31_signal) == sizeof(orion::psk31::Signal) && sizeof(orion_psk31_signal) == 32,
+              "orion_psk31_signal is psk31.hpp's record");
+static_assert(sizeof(orion_psk31_stream) == sizeof(orion::psk31::Stream) && sizeof(orion_psk31_stream) == 32 &&
+                  sizeof(orion_psk31_report) == 16 && ORION_PSK31_BPSK == orion::psk31::kBpsk &&
+                  ORION_PSK31_QPSK == orion::psk31::kQpsk,
+              "orion_psk31_stream is psk31.hpp's record");
+static_assert(ORION_VARICODE_MAX_BITS == orion::psk31::kVaricodeMaxBits &&
+                  ORION_PSK31_TRACEBACK_DEPTH == orion::psk31::kTracebackDepth,
+              "the header's constants are psk31.hpp's");
 static_assert(sizeof(orion_ft_signal) == sizeof(orion::ftmod::Signal) && sizeof(orion_ft_signal) == 24 &&
                   ORION_FT8_FRAME_LEN == 79 * 1920 && ORION_FT4_FRAME_LEN == 105 * 576,
               "orion_ft_signal is ftmod.hpp's record");
@@ -915,6 +950,423 @@ int orion_ft_demod_host(int protocol, float fs, float base_hz, const void* iq, u
   if (!iq || !tones) return fail(ORION_E_NULL, "null buffer");
   return guarded([&] {
     orion::ftmod::demodulate_host(protocol, fs, base_hz, static_cast<const float*>(iq), tones, energies);
+    return ORION_OK;
+  });
+}
+
+/* ---- PSK31 channel code (psk31.hpp, k_psk31.hip) ---- */
+int orion_psk31_tables(uint16_t* varicode_bits, uint8_t* varicode_len, float* dqpsk_exp) {
+  return guarded([&] {
+    const orion::psk31::Codeword* t = orion::psk31::varicode_table();
+    for (int i = 0; i < 128; ++i) {
+      if (varicode_bits) varicode_bits[i] = t[i].bits;
+      if (varicode_len) varicode_len[i] = t[i].len;
+    }
+    if (dqpsk_exp) std::memcpy(dqpsk_exp, orion::psk31::kDqpskExp, sizeof orion::psk31::kDqpskExp);
+    return ORION_OK;
+  });
+}
+int orion_varicode_encode(uint8_t byte, uint16_t* bits, uint8_t* len) {
+  if (!bits || !len) return fail(ORION_E_NULL, "null buffer");
+  const orion::psk31::Codeword c = orion::psk31::varicode_encode(byte);
+  *bits = c.bits;
+  *len = c.len;
+  return ORION_OK;
+}
+int orion_varicode_decode(uint16_t bits, uint8_t len) { return orion::psk31::varicode_decode(bits, len); }
+orion_varicode_encoder* orion_varicode_encoder_new(void) {
+  try {
+    return new orion_varicode_encoder;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_varicode_encoder_free(orion_varicode_encoder* e) { delete e; }
+int orion_varicode_encoder_push_preamble(orion_varicode_encoder* e, size_t n_bits) {
+  if (!e) return fail(ORION_E_NULL, "null handle");
+  if (n_bits > (1u << 30)) return fail(ORION_E_ARG, "varicode: more than 2^30 bits in one call");
+  return guarded([&] {
+    e->impl.push_preamble(n_bits);
+    return ORION_OK;
+  });
+}
+int orion_varicode_encoder_push_byte(orion_varicode_encoder* e, uint8_t byte) {
+  if (!e) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    e->impl.push_byte(byte);
+    return ORION_OK;
+  });
+}
+int orion_varicode_encoder_push_postamble(orion_varicode_encoder* e, size_t n_bits) {
+  if (!e) return fail(ORION_E_NULL, "null handle");
+  if (n_bits > (1u << 30)) return fail(ORION_E_ARG, "varicode: more than 2^30 bits in one call");
+  return guarded([&] {
+    e->impl.push_postamble(n_bits);
+    return ORION_OK;
+  });
+}
+size_t orion_varicode_encoder_pending(const orion_varicode_encoder* e) { return e ? e->impl.pending() : 0; }
+int orion_varicode_encoder_drain(orion_varicode_encoder* e, uint8_t* bits, size_t cap, size_t* n_bits) {
+  if (!e) return fail(ORION_E_NULL, "null handle");
+  if (!n_bits || (!bits && e->impl.pending())) return fail(ORION_E_NULL, "null buffer");
+  if (cap < e->impl.pending()) return fail(ORION_E_ARG, "varicode: capacity below the pending bits");
+  return guarded([&] {
+    const std::vector<uint8_t> v = e->impl.drain_bits();
+    if (!v.empty()) std::memcpy(bits, v.data(), v.size());
+    *n_bits = v.size();
+    return ORION_OK;
+  });
+}
+orion_varicode_decoder* orion_varicode_decoder_new(void) {
+  try {
+    return new orion_varicode_decoder;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_varicode_decoder_free(orion_varicode_decoder* d) { delete d; }
+int orion_varicode_decoder_push_bits(orion_varicode_decoder* d, const uint8_t* bits, size_t n) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  if (n && !bits) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    for (size_t i = 0; i < n; ++i) d->impl.push_bit(bits[i]);
+    return ORION_OK;
+  });
+}
+size_t orion_varicode_decoder_pending(const orion_varicode_decoder* d) { return d ? d->impl.pending() : 0; }
+int orion_varicode_decoder_pop_bytes(orion_varicode_decoder* d, uint8_t* bytes, size_t cap, size_t* n_bytes) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  if (!n_bytes || (!bytes && d->impl.pending())) return fail(ORION_E_NULL, "null buffer");
+  if (cap < d->impl.pending()) return fail(ORION_E_ARG, "varicode: capacity below the pending characters");
+  size_t k = 0;
+  for (int c; (c = d->impl.pop_char()) >= 0;) bytes[k++] = static_cast<uint8_t>(c);
+  *n_bytes = k;
+  return ORION_OK;
+}
+int orion_conv_encode(const uint8_t* bits, size_t n, uint8_t* coded) {
+  if (n && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
+  orion::psk31::conv_encode(bits, n, coded);
+  return ORION_OK;
+}
+int orion_psk31_viterbi(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits) {
+  if (nstreams && n_syms && (!soft || !bits)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31_viterbi_host(soft, nstreams, n_syms, bits);
+    return ORION_OK;
+  });
+}
+int orion_psk31_viterbi_device(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits, void* work,
+                               size_t work_bytes, void* stream) {
+  if (nstreams && n_syms && (!soft || !bits || !work)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31_viterbi(soft, nstreams, n_syms, bits, work, work_bytes, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_psk31_viterbi_work_bytes(size_t nstreams, size_t n_syms) {
+  if (nstreams > 0x7fffffffull - 3 || n_syms > 0x7fffffffull) return 0;
+  return orion::psk31::viterbi_work_bytes(nstreams, n_syms);
+}
+int orion_psk31_viterbi_host(const float* soft, size_t n_syms, uint8_t* bits) {
+  if (n_syms && (!soft || !bits)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31::viterbi_decode(soft, n_syms, bits);
+    return ORION_OK;
+  });
+}
+int orion_psk31_viterbi_hard_host(const uint8_t* coded, size_t n_syms, uint8_t* bits) {
+  if (n_syms && (!coded || !bits)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31::viterbi_decode_hard(coded, n_syms, bits);
+    return ORION_OK;
+  });
+}
+orion_psk31_streaming_viterbi* orion_psk31_streaming_viterbi_new(void) {
+  try {
+    return new orion_psk31_streaming_viterbi;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_psk31_streaming_viterbi_free(orion_psk31_streaming_viterbi* v) { delete v; }
+int orion_psk31_streaming_viterbi_feed(orion_psk31_streaming_viterbi* v, const float* soft, size_t n_syms,
+                                       uint8_t* bits, size_t* n_bits) {
+  if (!v) return fail(ORION_E_NULL, "null handle");
+  if (!n_bits || (n_syms && (!soft || !bits))) return fail(ORION_E_NULL, "null buffer");
+  size_t k = 0;
+  for (size_t i = 0; i < n_syms; ++i) {
+    const int b = v->impl.feed_symbol(soft[2 * i], soft[2 * i + 1]);
+    if (b >= 0) bits[k++] = static_cast<uint8_t>(b);
+  }
+  *n_bits = k;
+  return ORION_OK;
+}
+int orion_psk31_streaming_viterbi_flush(orion_psk31_streaming_viterbi* v, uint8_t* bits, size_t* n_bits) {
+  if (!v) return fail(ORION_E_NULL, "null handle");
+  if (!n_bits || !bits) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> out = v->impl.flush();
+    if (!out.empty()) std::memcpy(bits, out.data(), out.size());
+    *n_bits = out.size();
+    return ORION_OK;
+  });
+}
+
+/* ---- PSK31 modulators and demodulators (psk31.hpp, k_psk31.hip) ---- */
+size_t orion_psk31_sps(float fs) { return orion::psk31::psk31_sps(fs); }
+int orion_psk31_text_bits(const uint8_t* text, size_t n, size_t preamble_bits, size_t postamble_bits, uint8_t* bits,
+                          size_t cap, size_t* n_bits) {
+  if (!n_bits || (n && !text)) return fail(ORION_E_NULL, "null buffer");
+  if (n > (1u << 24) || preamble_bits > (1u << 30) || postamble_bits > (1u << 30))
+    return fail(ORION_E_ARG, "psk31 text: more than 2^24 bytes or 2^30 preamble / postamble bits");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::psk31::text_bits(text, n, preamble_bits, postamble_bits);
+    *n_bits = v.size();
+    if (cap < v.size()) return fail(ORION_E_ARG, "psk31 text: capacity below the bit count");
+    if (!v.empty()) {
+      if (!bits) return fail(ORION_E_NULL, "null buffer");
+      std::memcpy(bits, v.data(), v.size());
+    }
+    return ORION_OK;
+  });
+}
+orion_psk31_mod* orion_psk31_mod_new(int mode, float fs, float rf_hz, float gain) {
+  try {
+    return new orion_psk31_mod(mode, fs, rf_hz, gain);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_psk31_mod_free(orion_psk31_mod* m) { delete m; }
+int orion_psk31_mod_set_gain(orion_psk31_mod* m, float gain) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  m->impl.set_gain(gain);
+  return ORION_OK;
+}
+int orion_psk31_mod_reset(orion_psk31_mod* m) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  m->impl.reset();
+  return ORION_OK;
+}
+int orion_psk31_mod_modulate_bits(orion_psk31_mod* m, const uint8_t* bits, size_t n, void* iq) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  if (n && (!bits || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    m->impl.modulate_bits(bits, n, static_cast<float*>(iq));
+    return ORION_OK;
+  });
+}
+int orion_psk31_mod_modulate_bits_device(orion_psk31_mod* m, const uint8_t* bits, size_t n, void* iq, void* stream) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  if (n && (!bits || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    m->dev.modulate(bits, n, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_psk31_mod_modulate_batch(orion_psk31_mod* m, const uint8_t* bits, size_t nstreams, size_t n, void* iq) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  if (nstreams && n && (!bits || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    m->dev.modulate_batch_host(bits, nstreams, n, iq);
+    return ORION_OK;
+  });
+}
+int orion_psk31_mod_modulate_batch_device(orion_psk31_mod* m, const uint8_t* bits, size_t nstreams, size_t n, void* iq,
+                                          void* stream) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  if (nstreams && n && (!bits || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    m->dev.modulate_batch(bits, nstreams, n, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_psk31_synth(float fs, const orion_psk31_signal* signals, const uint8_t* bits, size_t nsig, size_t nch,
+                      size_t n_per_ch, int accumulate, void* iq) {
+  if ((nsig && !signals) || (nch && n_per_ch && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31_synth_host(fs, reinterpret_cast<const orion::psk31::Signal*>(signals), bits, nsig, nch, n_per_ch,
+                            accumulate != 0, iq);
+    return ORION_OK;
+  });
+}
+int orion_psk31_synth_device(float fs, const orion_psk31_signal* signals, const uint8_t* bits, size_t nsig, size_t nch,
+                             size_t n_per_ch, int accumulate, void* iq, void* stream) {
+  if ((nsig && !signals) || (nch && n_per_ch && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::psk31_synth(fs, reinterpret_cast<const orion::psk31::Signal*>(signals), bits, nsig, nch, n_per_ch,
+                       accumulate != 0, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+uint64_t orion_psk31_rotator_q64(float freq_hz, float fs) { return orion::psk31::rotator_step_q64(freq_hz, fs); }
+int orion_psk31_mod_process(orion_psk31_mod* m, const uint8_t* bits, size_t n_bits, void* iq, size_t out_cap,
+                            orion_work_report* report) {
+  if (!m) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n_bits && !bits) || (out_cap && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    m->impl.process(bits, n_bits, static_cast<float*>(iq), out_cap, &report->in_read, &report->out_written);
+    return ORION_OK;
+  });
+}
+orion_psk31_demod* orion_psk31_demod_new(int mode, float fs, float rf_hz, float gain, size_t offset) {
+  try {
+    return new orion_psk31_demod(mode, fs, rf_hz, gain, offset);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_psk31_demod_free(orion_psk31_demod* d) { delete d; }
+int orion_psk31_demod_set_gain(orion_psk31_demod* d, float gain) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  d->impl.set_gain(gain);
+  return ORION_OK;
+}
+int orion_psk31_demod_reset(orion_psk31_demod* d) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  d->impl.reset();
+  return ORION_OK;
+}
+int orion_psk31_demod_process(orion_psk31_demod* d, const void* iq, size_t n, float* soft, size_t out_cap,
+                              orion_work_report* report) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n && !iq) || (out_cap && !soft)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    d->impl.process(static_cast<const float*>(iq), n, soft, out_cap, &report->in_read, &report->out_written);
+    return ORION_OK;
+  });
+}
+int orion_bpsk31_decide(const float* soft, size_t n, uint8_t* bits) {
+  if (n && (!soft || !bits)) return fail(ORION_E_NULL, "null buffer");
+  orion::psk31::bpsk31_decide(soft, n, bits);
+  return ORION_OK;
+}
+int orion_psk31_find_carriers_host(const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                                   size_t min_carrier_syms, float peak_margin_db, size_t max_cand,
+                                   orion_candidate* cand, uint32_t* count) {
+  if (!cand || !count || (nch && num_syms && num_bins && !wf)) return fail(ORION_E_NULL, "null buffer");
+  if (max_cand == 0) return fail(ORION_E_ARG, "max_cand == 0");
+  if (max_cand > (1u << 16)) return fail(ORION_E_ARG, "max_cand above 65536");
+  if (nch > 65535 || num_syms > 0x7fffffffull || num_bins > 0x7fffffffull ||
+      static_cast<unsigned long long>(nch) * num_syms * num_bins > 0x7fffffffull)
+    return fail(ORION_E_ARG, "psk31 carrier search: nch <= 65535 and a waterfall below 2^31 cells");
+  return guarded([&] {
+    for (size_t ch = 0; ch < nch; ++ch) {
+      const std::vector<orion::psk31::Carrier> v = orion::psk31::find_carriers(
+          wf + ch * num_syms * num_bins, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand);
+      count[ch] = static_cast<uint32_t>(v.size());
+      for (size_t k = 0; k < max_cand; ++k) {
+        orion_candidate& c = cand[ch * max_cand + k];
+        c = orion_candidate{0, 0u, 0.0f};
+        if (k < v.size()) c = orion_candidate{v[k].time_sym, v[k].freq_bin, v[k].score};
+      }
+    }
+    return ORION_OK;
+  });
+}
+int orion_psk31_find_carriers(orion_sync* h, const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                              size_t min_carrier_syms, float peak_margin_db, size_t max_cand, orion_candidate* cand,
+                              uint32_t* count) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!cand || !count || (nch && num_syms && num_bins && !wf)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->psk.find_carriers_host(wf, nch, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand,
+                              reinterpret_cast<orion::SyncCandidate*>(cand), count);
+    return ORION_OK;
+  });
+}
+int orion_psk31_find_carriers_device(orion_sync* h, const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                                     size_t min_carrier_syms, float peak_margin_db, size_t max_cand,
+                                     orion_candidate* cand, uint32_t* count, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!cand || !count || (nch && num_syms && num_bins && !wf)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->psk.find_carriers(wf, nch, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand,
+                         reinterpret_cast<orion::SyncCandidate*>(cand), count, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_psk31_sync(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
+                     size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand,
+                     orion_candidate* cand, uint32_t* count, float* soft, orion_psk31_report* reports) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || !reports || (max_cand && (!cand || !soft))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->psk.sync_host(h->impl, iq, nch, n_per_ch, fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand,
+                     reinterpret_cast<orion::SyncCandidate*>(cand), count, soft, reinterpret_cast<uint64_t*>(reports));
+    return ORION_OK;
+  });
+}
+int orion_psk31_sync_device(orion_sync* h, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz,
+                            float max_hz, size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand,
+                            orion_candidate* cand, uint32_t* count, float* soft, orion_psk31_report* reports,
+                            void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((!iq && n_per_ch) || !count || !reports || (max_cand && (!cand || !soft))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->psk.sync(h->impl, iq, nch, n_per_ch, fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand,
+                reinterpret_cast<orion::SyncCandidate*>(cand), count, soft, reinterpret_cast<uint64_t*>(reports),
+                static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_psk31_sync_num_bins(float base_hz, float max_hz) {
+  try {
+    return orion::psk31::sync_num_bins(base_hz, max_hz);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 0;
+  }
+}
+orion_psk31_demod_bank* orion_psk31_demod_bank_new(float fs, const orion_psk31_stream* streams, size_t nstreams,
+                                                   size_t nch) {
+  if (!streams) {
+    g_err = "null buffer";
+    return nullptr;
+  }
+  try {
+    return new orion_psk31_demod_bank(fs, reinterpret_cast<const orion::psk31::Stream*>(streams), nstreams, nch);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_psk31_demod_bank_free(orion_psk31_demod_bank* b) { delete b; }
+int orion_psk31_demod_bank_process(orion_psk31_demod_bank* b, const void* iq, size_t nch, size_t n, float* soft,
+                                   size_t out_stride, uint8_t* bits, orion_psk31_report* reports) {
+  if (!b) return fail(ORION_E_NULL, "null handle");
+  if ((n && !iq) || !reports || (out_stride && !soft)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    b->impl.process_host(iq, nch, n, soft, out_stride, bits, reinterpret_cast<uint64_t*>(reports));
+    return ORION_OK;
+  });
+}
+int orion_psk31_demod_bank_process_device(orion_psk31_demod_bank* b, const void* iq, size_t nch, size_t n, float* soft,
+                                          size_t out_stride, uint8_t* bits, orion_psk31_report* reports, void* stream) {
+  if (!b) return fail(ORION_E_NULL, "null handle");
+  if ((n && !iq) || !reports || (out_stride && !soft)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    b->impl.process(iq, nch, n, soft, out_stride, bits, reinterpret_cast<uint64_t*>(reports),
+                    static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_psk31_demod_bank_set_gain(orion_psk31_demod_bank* b, size_t index, float gain) {
+  if (!b) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    b->impl.set_gain(index, gain);
+    return ORION_OK;
+  });
+}
+int orion_psk31_demod_bank_reset(orion_psk31_demod_bank* b) {
+  if (!b) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    b->impl.reset();
     return ORION_OK;
   });
 }

@@ -8,6 +8,7 @@
 
 #include "ftmod.hpp"
 #include "hip_common.hpp"
+#include "psk31.hpp"
 
 namespace orion {
 
@@ -234,4 +235,44 @@ void launch_ft_synth(bool ft4, const FtSynthRecord* rec_dev, const uint32_t* row
 // f32 [nframes][79 | 105][8 | 4].
 void launch_ft_demod(bool ft4, const f2* x_dev, int nframes, long long n, const float* steps, uint8_t* tones_dev,
                      float* energies_dev, hipStream_t s);
+
+// ------------------------------------- PSK31 channel code: batched Viterbi (k_psk31.hip) --
+// viterbi_decode (codec/psk31.rs:95-160) of nstreams soft streams: soft_dev [nstreams][2 *
+// n_syms] f32 -> bits_dev [nstreams][n_syms] u8. work_dev: psk31::viterbi_work_bytes bytes of
+// scratch, 4-byte aligned. nstreams <= 2^31 - 4, n_syms <= 2^31 - 1.
+void launch_psk31_viterbi(const float* soft_dev, long long nstreams, long long n_syms, uint8_t* bits_dev,
+                          uint32_t* work_dev, hipStream_t s);
+// The demodulator bank: one launch advances nstreams demodulators over x_dev [nch][n] cf32,
+// whose first sample is the channels' sample base. rec_dev [nstreams] sorted by channel
+// (every channel < nch, every out_cap <= out_stride), st_dev [nstreams] carried from call to
+// call, hann_dev [sps]. soft_dev [nstreams][out_stride] and bits_dev (optional; soft >= 0, BPSK31 streams only)
+// are indexed by the record's slot; report_dev [nstreams][2] = {in_read, out_written}.
+void launch_psk31_demod(const f2* x_dev, long long n, unsigned long long base, const psk31::BankRecord* rec_dev,
+                        psk31::DemodState* st_dev, int nstreams, const float* hann_dev, uint32_t sps, float* soft_dev,
+                        long long out_stride, uint8_t* bits_dev, unsigned long long* report_dev, hipStream_t s);
+// psk31_sync's carrier search (sync/psk31_sync.rs:82-203) on wf_dev [nch][num_syms][num_bins]
+// (log waterfall): cand_dev [nch][max_cand] in the order psk31.hpp find_carriers defines
+// (unused slots zeroed), count_dev [nch]. Scratch: med_dev [nch][num_bins] f32, floor_dev [nch]
+// f32, runs_dev [nch][num_bins][max_cand], nruns_dev and head_dev [nch][num_bins] u32.
+// ln_margin = peak_margin_db * LN_2 / 3 in f32; min_run >= 1; max_cand >= 1.
+void launch_psk31_carriers(const float* wf_dev, int nch, int num_syms, int num_bins, int min_run, float ln_margin,
+                           int max_cand, float* med_dev, float* floor_dev, SyncCandidate* runs_dev, uint32_t* nruns_dev,
+                           uint32_t* head_dev, SyncCandidate* cand_dev, uint32_t* count_dev, hipStream_t s);
+// The candidates' bank records and initial states, written on the device (record_candidate,
+// psk31_sync.rs:209-239): rec_dev / st_dev [nch * max_cand], slot = channel * max_cand + k.
+// steps_dev [num_bins][3]: each bin's Rotator step (w_re, w_im) and 1 if it has a rotator.
+void launch_psk31_cand_records(const SyncCandidate* cand_dev, const uint32_t* count_dev, int nch, int max_cand,
+                               const float* steps_dev, uint32_t sps, uint32_t out_cap, float scale,
+                               psk31::BankRecord* rec_dev, psk31::DemodState* st_dev, hipStream_t s);
+// The PSK31 modulator for a batch of streams: ph_dev [nstreams][n_syms + 1] symbol phasors
+// (psk31.hpp Mod::symbol_phasors), hann_dev [sps], rot_dev (optional) >= n_syms * sps Rotator
+// phasors from a fresh start; out_dev [nstreams][n_syms * sps] cf32.
+void launch_psk31_mod(const f2* ph_dev, const float* hann_dev, const f2* rot_dev, int nstreams, long long n_syms,
+                      uint32_t sps, float gain, f2* out_dev, hipStream_t s);
+// PSK31 band synthesis: out_dev [nch][n] cf32 = (accumulate ? out : 0) + the signals of each
+// channel in table order. rec_dev sorted by channel, rows_dev [nch + 1], ph_dev the signals'
+// symbol phasors concatenated (n_bits + 1 each), hann_dev [sps].
+void launch_psk31_synth(const psk31::SynthRecord* rec_dev, const uint32_t* rows_dev, const f2* ph_dev,
+                        const float* hann_dev, uint32_t sps, int nch, long long n, bool accumulate, f2* out_dev,
+                        hipStream_t s);
 }  // namespace orion

@@ -1,0 +1,385 @@
+// psk31_blocks.cpp — host side of the PSK31 kernels (psk31_blocks.hpp).
+#include "psk31_blocks.hpp"
+
+#include <algorithm>
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+namespace orion {
+
+namespace {
+constexpr size_t kMaxCh = 65535;  // channels ride a 32-bit record field; the limit of the sync entries
+}  // namespace
+
+// ---- the batched Viterbi decode ----
+void psk31_viterbi(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits, void* work, size_t work_bytes,
+                   hipStream_t s) {
+  if (nstreams > 0x7fffffffull - 3 || n_syms > 0x7fffffffull)
+    throw std::invalid_argument("psk31 viterbi: nstreams <= 2^31 - 4 and n_syms <= 2^31 - 1");
+  if (nstreams == 0 || n_syms == 0) return;
+  if (!work || work_bytes < psk31::viterbi_work_bytes(nstreams, n_syms))
+    throw std::invalid_argument("psk31 viterbi: work below orion_psk31_viterbi_work_bytes(nstreams, n_syms)");
+  if (reinterpret_cast<uintptr_t>(work) % 4 || reinterpret_cast<uintptr_t>(soft) % 4)
+    throw std::invalid_argument("psk31 viterbi: soft / work not 4-byte aligned");
+  launch_psk31_viterbi(soft, static_cast<long long>(nstreams), static_cast<long long>(n_syms), bits,
+                       static_cast<uint32_t*>(work), s);
+}
+
+void psk31_viterbi_host(const float* soft, size_t nstreams, size_t n_syms, uint8_t* bits) {
+  if (nstreams > 0x7fffffffull - 3 || n_syms > 0x7fffffffull)
+    throw std::invalid_argument("psk31 viterbi: nstreams <= 2^31 - 4 and n_syms <= 2^31 - 1");
+  if (nstreams == 0 || n_syms == 0) return;
+  const size_t sb = nstreams * n_syms * 2 * sizeof(float), bb = nstreams * n_syms;
+  const size_t wb = psk31::viterbi_work_bytes(nstreams, n_syms);
+  DevBuf d_soft(sb), d_bits(bb + 16), d_work(wb);
+  ORION_HIP(hipMemcpy(d_soft.as<void>(), soft, sb, hipMemcpyHostToDevice));
+  psk31_viterbi(d_soft.as<float>(), nstreams, n_syms, d_bits.as<uint8_t>(), d_work.as<void>(), wb, nullptr);
+  ORION_HIP(hipMemcpy(bits, d_bits.as<void>(), bb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+// ---- the demodulator bank ----
+Psk31DemodBank::Psk31DemodBank(float fs, const psk31::Stream* streams, size_t nstreams, size_t nch) : nch_(nch) {
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("psk31 bank: 1 <= nch <= 65535");
+  if (nstreams < 1 || nstreams > (1u << 24)) throw std::invalid_argument("psk31 bank: 1 <= nstreams <= 2^24");
+  std::vector<size_t> order(nstreams);
+  for (size_t k = 0; k < nstreams; ++k) {
+    if (streams[k].channel >= nch) throw std::invalid_argument("psk31 bank: a stream's channel >= nch");
+    if (streams[k].out_cap > (1u << 30)) throw std::invalid_argument("psk31 bank: out_cap above 2^30");
+    order[k] = k;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return streams[a].channel != streams[b].channel ? streams[a].channel < streams[b].channel
+                                                    : streams[a].start < streams[b].start;
+  });
+  rec_.resize(nstreams);
+  st0_.resize(nstreams);
+  // the window, its square sum and the initial state are the host demodulator's own (one
+  // stream's constructor: they do not depend on the stream); the first count does
+  const psk31::Demod proto(psk31::kBpsk, fs, 0.0f, 1.0f, 0);
+  sps_ = proto.sps();
+  hann_ = proto.hann();
+  hann_sq_sum_ = proto.hann_sq_sum();
+  for (size_t j = 0; j < nstreams; ++j) {
+    const psk31::Stream& t = streams[order[j]];
+    if (t.mode != static_cast<uint32_t>(psk31::kBpsk) && t.mode != static_cast<uint32_t>(psk31::kQpsk))
+      throw std::invalid_argument("psk31: unknown mode (ORION_PSK31_BPSK / ORION_PSK31_QPSK)");
+    psk31::BankRecord& r = rec_[j];
+    r.start = t.start;
+    r.mode = t.mode;
+    r.channel = t.channel;
+    r.slot = static_cast<uint32_t>(order[j]);
+    r.out_cap = t.out_cap;
+    r.rot = t.rf_hz != 0.0f ? 1u : 0u;
+    r.w_re = 1.0f;
+    r.w_im = 0.0f;
+    if (r.rot) psk31::rotator_step(-t.rf_hz, fs, &r.w_re, &r.w_im);
+    r.scale = t.gain / hann_sq_sum_;
+    st0_[j] = proto.state();
+    st0_[j].count = psk31::demod_start_count(sps_, t.offset);
+    max_cap_ = std::max(max_cap_, static_cast<size_t>(t.out_cap));
+  }
+}
+
+void Psk31DemodBank::set_gain(size_t slot, float gain) {
+  for (psk31::BankRecord& r : rec_)
+    if (r.slot == slot) {
+      r.scale = gain / hann_sq_sum_;
+      rec_dirty_ = true;
+      return;
+    }
+  throw std::invalid_argument("psk31 bank: no such stream");
+}
+
+void Psk31DemodBank::reset() {
+  if (d_st_.size()) ORION_HIP(hipDeviceSynchronize());  // launches in flight still carry the old states
+  base_ = 0;
+  fresh_ = true;
+}
+
+void Psk31DemodBank::process(const void* iq, size_t nch, size_t n, float* soft, size_t out_stride, uint8_t* bits,
+                             uint64_t* reports, hipStream_t s) {
+  if (nch != nch_) throw std::invalid_argument("psk31 bank: nch is not the bank's");
+  if (out_stride < max_cap_) throw std::invalid_argument("psk31 bank: out_stride below the largest out_cap");
+  if (n > (1ull << 40) || out_stride > (1ull << 31))
+    throw std::invalid_argument("psk31 bank: n above 2^40 or out_stride above 2^31");
+  const auto misaligned = [](const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+  if (misaligned(iq, 8) || misaligned(reports, 8) || misaligned(soft, 4))
+    throw std::invalid_argument("psk31 bank: iq / reports not 8-byte aligned, or soft not 4-byte aligned");
+  if (fresh_) {
+    d_rec_.upload(rec_.data(), rec_.size() * sizeof(psk31::BankRecord), s);
+    d_st_.upload(st0_.data(), st0_.size() * sizeof(psk31::DemodState), s);
+    d_hann_.upload(hann_.data(), hann_.size() * sizeof(float), s);
+    fresh_ = false;
+    rec_dirty_ = false;
+  }
+  if (rec_dirty_) {
+    ORION_HIP(hipDeviceSynchronize());  // launches in flight read the old records
+    d_rec_.upload(rec_.data(), rec_.size() * sizeof(psk31::BankRecord), s);
+    rec_dirty_ = false;
+  }
+  launch_psk31_demod(static_cast<const f2*>(iq), static_cast<long long>(n), base_, d_rec_.as<psk31::BankRecord>(),
+                     d_st_.as<psk31::DemodState>(), static_cast<int>(rec_.size()), d_hann_.as<float>(),
+                     static_cast<uint32_t>(sps_), soft, static_cast<long long>(out_stride), bits,
+                     reinterpret_cast<unsigned long long*>(reports), s);
+  base_ += n;
+}
+
+void Psk31DemodBank::process_host(const void* iq, size_t nch, size_t n, float* soft, size_t out_stride, uint8_t* bits,
+                                  uint64_t* reports) {
+  if (nch != nch_) throw std::invalid_argument("psk31 bank: nch is not the bank's");
+  if (out_stride < max_cap_) throw std::invalid_argument("psk31 bank: out_stride below the largest out_cap");
+  const size_t ns = rec_.size(), ib = nch * n * 8, sb = ns * out_stride * sizeof(float), bb = bits ? ns * out_stride : 0;
+  const size_t rb = ns * 2 * sizeof(uint64_t);
+  h_iq_.resize(ib + 16);
+  h_soft_.resize(sb + 16);
+  h_bits_.resize(bb + 16);
+  h_rep_.resize(rb);
+  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  if (sb) ORION_HIP(hipMemset(h_soft_.as<void>(), 0, sb));
+  if (bb) ORION_HIP(hipMemset(h_bits_.as<void>(), 0, bb));
+  process(h_iq_.as<void>(), nch, n, h_soft_.as<float>(), out_stride, bits ? h_bits_.as<uint8_t>() : nullptr,
+          h_rep_.as<uint64_t>(), nullptr);
+  if (sb) ORION_HIP(hipMemcpy(soft, h_soft_.as<void>(), sb, hipMemcpyDeviceToHost));
+  if (bb) ORION_HIP(hipMemcpy(bits, h_bits_.as<void>(), bb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(reports, h_rep_.as<void>(), rb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+// ---- the modulator ----
+void Psk31ModDev::run(const std::vector<float>& ph, size_t nstreams, size_t n, void* iq_dev, hipStream_t s) {
+  const size_t sps = host_.sps(), per = n * sps;
+  if (nstreams > 0x7fffffffull || per > (1ull << 40)) throw std::invalid_argument("psk31 mod: batch too large");
+  if (reinterpret_cast<uintptr_t>(iq_dev) % 8) throw std::invalid_argument("psk31 mod: iq not 8-byte aligned");
+  if (nstreams == 0 || n == 0) return;
+  if (hann_.size() == 0) hann_.upload(host_.hann().data(), sps * sizeof(float), s);
+  if (host_.rf_hz() != 0.0f && rot_n_ < per) {  // a fresh Rotator per call: any call's phasors are a prefix
+    ORION_HIP(hipDeviceSynchronize());          // launches in flight read the table that is replaced
+    std::vector<float> z(2 * per);
+    psk31::rotator_table(host_.rf_hz(), host_.fs(), per, z.data());
+    rot_.upload(z.data(), z.size() * sizeof(float), s);
+    rot_n_ = per;
+  }
+  ph_.upload(ph.data(), ph.size() * sizeof(float), s);
+  launch_psk31_mod(ph_.as<f2>(), hann_.as<float>(), host_.rf_hz() != 0.0f ? rot_.as<f2>() : nullptr,
+                   static_cast<int>(nstreams), static_cast<long long>(n), static_cast<uint32_t>(sps), host_.gain(),
+                   static_cast<f2*>(iq_dev), s);
+  ORION_HIP(hipStreamSynchronize(s));  // ph_ is rewritten by the next call
+}
+
+void Psk31ModDev::modulate(const uint8_t* bits, size_t n, void* iq_dev, hipStream_t s) {
+  std::vector<float> ph(2 * (n + 1));
+  host_.symbol_phasors(bits, n, ph.data());
+  run(ph, 1, n, iq_dev, s);
+}
+
+void Psk31ModDev::modulate_batch(const uint8_t* bits, size_t nstreams, size_t n, void* iq_dev, hipStream_t s) {
+  if (nstreams > (1u << 24) || n > (1ull << 32)) throw std::invalid_argument("psk31 mod: nstreams <= 2^24, n <= 2^32");
+  std::vector<float> ph(2 * (n + 1) * nstreams);
+  for (size_t k = 0; k < nstreams; ++k) {
+    psk31::Mod fresh(host_.mode(), host_.fs(), host_.rf_hz(), host_.gain());
+    fresh.symbol_phasors(bits + k * n, n, ph.data() + 2 * (n + 1) * k);
+  }
+  run(ph, nstreams, n, iq_dev, s);
+}
+
+void Psk31ModDev::modulate_batch_host(const uint8_t* bits, size_t nstreams, size_t n, void* iq) {
+  const size_t ob = nstreams * n * host_.sps() * 8;
+  if (ob == 0) return;
+  h_out_.resize(ob);
+  modulate_batch(bits, nstreams, n, h_out_.as<void>(), nullptr);
+  ORION_HIP(hipMemcpy(iq, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+// ---- band synthesis ----
+void psk31_synth(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
+                 bool accumulate, void* iq_dev, hipStream_t s) {
+  static std::mutex mu;
+  static DevBuf d_rec, d_rows, d_ph, d_hann;
+  static float hann_fs = 0.0f;
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("psk31 synth: 1 <= nch <= 65535");
+  if (nsig > (1u << 24) || n > (1ull << 40)) throw std::invalid_argument("psk31 synth: nsig <= 2^24, n <= 2^40");
+  if (reinterpret_cast<uintptr_t>(iq_dev) % 8) throw std::invalid_argument("psk31 synth: iq not 8-byte aligned");
+  const psk31::Mod proto(psk31::kBpsk, fs, 0.0f, 1.0f);  // checks fs; the window
+  const size_t sps = proto.sps();
+  std::vector<size_t> order(nsig), first(nsig);
+  size_t total_bits = 0;
+  for (size_t k = 0; k < nsig; ++k) {
+    if (signals[k].channel >= nch) throw std::invalid_argument("psk31 synth: a signal's channel >= nch");
+    if (signals[k].n_bits > (1ull << 32)) throw std::invalid_argument("psk31 synth: n_bits above 2^32");
+    order[k] = k;
+    first[k] = total_bits;
+    total_bits += signals[k].n_bits;
+  }
+  if (total_bits > (1ull << 34)) throw std::invalid_argument("psk31 synth: more than 2^34 bits");
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return signals[a].channel < signals[b].channel; });
+  std::vector<psk31::SynthRecord> rec(nsig);
+  std::vector<uint32_t> rows(nch + 1, 0);
+  std::vector<float> ph(2 * (total_bits + nsig) + 2);
+  size_t at = 0;
+  for (size_t j = 0; j < nsig; ++j) {
+    const psk31::Signal& g = signals[order[j]];
+    psk31::Mod fresh(static_cast<int>(g.mode), fs, g.rf_hz, g.gain);
+    fresh.symbol_phasors(bits + first[order[j]], g.n_bits, ph.data() + 2 * at);
+    rec[j] = {g.offset, static_cast<int64_t>(g.n_bits * sps), at, psk31::rotator_step_q64(g.rf_hz, fs), g.gain,
+              g.rf_hz != 0.0f ? 1u : 0u};
+    // an offset this far out never meets the channel; keep the kernel's i - offset inside int64
+    if (g.offset < -(1LL << 62) || g.offset > (1LL << 62)) rec[j].len = 0;
+    at += g.n_bits + 1;
+    rows[g.channel + 1] += 1;
+  }
+  for (size_t ch = 0; ch < nch; ++ch) rows[ch + 1] += rows[ch];
+  std::lock_guard<std::mutex> lock(mu);
+  ORION_HIP(hipDeviceSynchronize());  // an earlier launch may still read the plan that is replaced
+  if (hann_fs != fs || d_hann.size() == 0) {
+    d_hann.upload(proto.hann().data(), sps * sizeof(float), s);
+    hann_fs = fs;
+  }
+  rec.resize(nsig + 1);  // never an empty upload
+  d_rec.upload(rec.data(), rec.size() * sizeof(psk31::SynthRecord), s);
+  d_rows.upload(rows.data(), rows.size() * sizeof(uint32_t), s);
+  d_ph.upload(ph.data(), ph.size() * sizeof(float), s);
+  launch_psk31_synth(d_rec.as<psk31::SynthRecord>(), d_rows.as<uint32_t>(), d_ph.as<f2>(), d_hann.as<float>(),
+                     static_cast<uint32_t>(sps), static_cast<int>(nch), static_cast<long long>(n), accumulate,
+                     static_cast<f2*>(iq_dev), s);
+}
+
+void psk31_synth_host(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
+                      bool accumulate, void* iq) {
+  const size_t ob = nch * n * 8;
+  DevBuf d_out(ob + 16);
+  if (ob && accumulate) ORION_HIP(hipMemcpy(d_out.as<void>(), iq, ob, hipMemcpyHostToDevice));
+  psk31_synth(fs, signals, bits, nsig, nch, n, accumulate, d_out.as<void>(), nullptr);
+  if (ob) ORION_HIP(hipMemcpy(iq, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+// ---- psk31_sync on the device ----
+namespace {
+constexpr size_t kMaxCand = 1u << 16;
+void check_search(size_t nch, size_t num_syms, size_t num_bins, size_t max_cand) {
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");  // as the FT entries
+  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("psk31 sync: 1 <= nch <= 65535");
+  if (num_syms > 0x7fffffffull || num_bins > (1u << 24) || nch * num_syms * num_bins > 0x7fffffffull)
+    throw std::invalid_argument("psk31 sync: waterfall above 2^31 - 1 cells");
+  if (nch * num_bins * max_cand > (1ull << 26) || num_bins * max_cand > (1ull << 22))
+    throw std::invalid_argument("psk31 sync: nch * num_bins * max_cand <= 2^26 and num_bins * max_cand <= 2^22");
+}
+}  // namespace
+
+void Psk31Sync::find_carriers(const float* wf, size_t nch, size_t num_syms, size_t num_bins, size_t min_carrier_syms,
+                              float peak_margin_db, size_t max_cand, SyncCandidate* cand, uint32_t* count,
+                              hipStream_t s) {
+  check_search(nch, num_syms, num_bins, max_cand);
+  const float ln_margin = peak_margin_db * 0.693147180559945309417f / 3.0f;  // psk31_sync.rs:82
+  const size_t min_run = min_carrier_syms > 1 ? min_carrier_syms : 1;
+  med_.resize((nch * num_bins + 1) * sizeof(float));
+  floor_.resize(nch * sizeof(float));
+  runs_.resize((nch * num_bins * max_cand + 1) * sizeof(SyncCandidate));
+  nruns_.resize((nch * num_bins + 1) * sizeof(uint32_t));
+  head_.resize((nch * num_bins + 1) * sizeof(uint32_t));
+  launch_psk31_carriers(wf, static_cast<int>(nch), static_cast<int>(num_syms), static_cast<int>(num_bins),
+                        static_cast<int>(min_run > 0x7fffffffull ? 0x7fffffffull : min_run), ln_margin,
+                        static_cast<int>(max_cand), med_.as<float>(), floor_.as<float>(), runs_.as<SyncCandidate>(),
+                        nruns_.as<uint32_t>(), head_.as<uint32_t>(), cand, count, s);
+}
+
+void Psk31Sync::sync(Sync& eng, const void* iq, size_t nch, size_t n, float fs, float base_hz, float max_hz,
+                     size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand, SyncCandidate* cand,
+                     uint32_t* count, float* soft, uint64_t* reports, hipStream_t s) {
+  if (n_bits > (1u << 30) - 2) throw std::invalid_argument("psk31 sync: n_bits above 2^30 - 2");
+  if (reinterpret_cast<uintptr_t>(iq) % 8 || reinterpret_cast<uintptr_t>(reports) % 8)
+    throw std::invalid_argument("psk31 sync: iq / reports not 8-byte aligned");
+  const size_t num_bins = psk31::sync_num_bins(base_hz, max_hz);
+  const size_t sps = psk31::psk31_sps(fs);
+  const size_t num_syms = sps ? n / sps : 0;
+  check_search(nch, num_syms, num_bins, max_cand);
+  const size_t slots = nch * max_cand, stride = n_bits + 2;
+  if (slots * stride > (1ull << 32)) throw std::invalid_argument("psk31 sync: nch * max_cand * (n_bits + 2) above 2^32");
+  ORION_HIP(hipMemsetAsync(soft, 0, slots * stride * sizeof(float), s));
+  ORION_HIP(hipMemsetAsync(reports, 0, slots * 2 * sizeof(uint64_t), s));
+  if (num_syms == 0) {  // psk31_sync.rs:60-68: no candidates
+    ORION_HIP(hipMemsetAsync(cand, 0, slots * sizeof(SyncCandidate), s));
+    ORION_HIP(hipMemsetAsync(count, 0, nch * sizeof(uint32_t), s));
+    return;
+  }
+  if (fs != hann_fs_ || hann_.size() == 0) {
+    const psk31::Demod proto(psk31::kBpsk, fs, 0.0f, 1.0f, 0);
+    hann_.upload(proto.hann().data(), proto.hann().size() * sizeof(float), s);
+    hann_sq_sum_ = proto.hann_sq_sum();
+    hann_fs_ = fs;
+    st_bins_ = 0;
+  }
+  if (num_bins != st_bins_ || fs != st_fs_ || base_hz != st_base_) {
+    // each bin's carrier as record_candidate computes it, and Bpsk31Demod::new's Rotator step
+    std::vector<float> w(3 * num_bins);
+    for (size_t b = 0; b < num_bins; ++b) {
+      const float carrier = base_hz + static_cast<float>(b) * 31.25f;
+      w[3 * b] = 1.0f;
+      w[3 * b + 1] = 0.0f;
+      w[3 * b + 2] = carrier != 0.0f ? 1.0f : 0.0f;
+      if (carrier != 0.0f) psk31::rotator_step(-carrier, fs, &w[3 * b], &w[3 * b + 1]);
+    }
+    steps_.upload(w.data(), w.size() * sizeof(float), s);
+    st_bins_ = num_bins;
+    st_fs_ = fs;
+    st_base_ = base_hz;
+  }
+  wf_.resize(nch * num_syms * num_bins * sizeof(float));
+  rec_.resize(slots * sizeof(psk31::BankRecord));
+  st_.resize(slots * sizeof(psk31::DemodState));
+  eng.waterfall(iq, fs, base_hz, 31.25f, sps, num_syms, num_bins, 0, nch, n, kWfLog, wf_.as<float>(), s);
+  find_carriers(wf_.as<float>(), nch, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand, cand, count, s);
+  launch_psk31_cand_records(cand, count, static_cast<int>(nch), static_cast<int>(max_cand), steps_.as<float>(),
+                            static_cast<uint32_t>(sps), static_cast<uint32_t>(stride), 1.0f / hann_sq_sum_,
+                            rec_.as<psk31::BankRecord>(), st_.as<psk31::DemodState>(), s);
+  launch_psk31_demod(static_cast<const f2*>(iq), static_cast<long long>(n), 0ull, rec_.as<psk31::BankRecord>(),
+                     st_.as<psk31::DemodState>(), static_cast<int>(slots), hann_.as<float>(), static_cast<uint32_t>(sps),
+                     soft, static_cast<long long>(stride), nullptr, reinterpret_cast<unsigned long long*>(reports), s);
+}
+
+void Psk31Sync::find_carriers_host(const float* wf, size_t nch, size_t num_syms, size_t num_bins,
+                                   size_t min_carrier_syms, float peak_margin_db, size_t max_cand, SyncCandidate* cand,
+                                   uint32_t* count) {
+  check_search(nch, num_syms, num_bins, max_cand);
+  const size_t wb = nch * num_syms * num_bins * sizeof(float), cb = nch * max_cand * sizeof(SyncCandidate);
+  h_in_.resize(wb + 16);
+  h_cand_.resize(cb);
+  h_count_.resize(nch * sizeof(uint32_t));
+  if (wb) ORION_HIP(hipMemcpy(h_in_.as<void>(), wf, wb, hipMemcpyHostToDevice));
+  find_carriers(h_in_.as<float>(), nch, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand,
+                h_cand_.as<SyncCandidate>(), h_count_.as<uint32_t>(), nullptr);
+  ORION_HIP(hipMemcpy(cand, h_cand_.as<void>(), cb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(count, h_count_.as<void>(), nch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+void Psk31Sync::sync_host(Sync& eng, const void* iq, size_t nch, size_t n, float fs, float base_hz, float max_hz,
+                          size_t min_carrier_syms, float peak_margin_db, size_t n_bits, size_t max_cand,
+                          SyncCandidate* cand, uint32_t* count, float* soft, uint64_t* reports) {
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  if (max_cand > kMaxCand || nch < 1 || nch > kMaxCh || n_bits > (1u << 30) - 2)
+    throw std::invalid_argument("psk31 sync: 1 <= nch <= 65535, max_cand <= 65536, n_bits <= 2^30 - 2");
+  const size_t slots = nch * max_cand, stride = n_bits + 2;
+  if (slots * stride > (1ull << 32)) throw std::invalid_argument("psk31 sync: nch * max_cand * (n_bits + 2) above 2^32");
+  const size_t ib = nch * n * 8, cb = slots * sizeof(SyncCandidate), sb = slots * stride * sizeof(float);
+  const size_t rb = slots * 2 * sizeof(uint64_t);
+  h_in_.resize(ib + 16);
+  h_cand_.resize(cb);
+  h_count_.resize(nch * sizeof(uint32_t));
+  h_soft_.resize(sb);
+  h_rep_.resize(rb);
+  if (ib) ORION_HIP(hipMemcpy(h_in_.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  sync(eng, h_in_.as<void>(), nch, n, fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand,
+       h_cand_.as<SyncCandidate>(), h_count_.as<uint32_t>(), h_soft_.as<float>(), h_rep_.as<uint64_t>(), nullptr);
+  ORION_HIP(hipMemcpy(cand, h_cand_.as<void>(), cb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(count, h_count_.as<void>(), nch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(soft, h_soft_.as<void>(), sb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipMemcpy(reports, h_rep_.as<void>(), rb, hipMemcpyDeviceToHost));
+  ORION_HIP(hipDeviceSynchronize());
+}
+
+}  // namespace orion

@@ -36,6 +36,11 @@ __all__ = [
     "ldpc_tables", "ft_crc14", "ft8_decode", "ft4_decode", "ft8_decode_batch", "ft4_decode_batch",
     "Ft8Mod", "Ft4Mod", "Ft8Demod", "Ft4Demod", "ft8_synth", "ft4_synth", "SIGNAL_DTYPE", "FT8_FRAME_LEN",
     "FT4_FRAME_LEN",
+    "VaricodeEncoder", "VaricodeDecoder", "StreamingViterbi", "varicode_encode", "varicode_decode", "psk31_tables",
+    "conv_encode", "viterbi_decode", "viterbi_decode_hard", "psk31_viterbi_batch", "VARICODE_MAX_BITS",
+    "PSK31_TRACEBACK_DEPTH", "psk31_sps", "psk31_text_bits", "Bpsk31Mod", "Qpsk31Mod", "Bpsk31Demod", "Qpsk31Demod",
+    "Bpsk31Decider", "Psk31DemodBank", "PSK31_STREAM_DTYPE", "PSK31_REPORT_DTYPE", "psk31_find_carriers", "psk31_find_carriers_device", "psk31_synth", "PSK31_SIGNAL_DTYPE", "psk31_rotator_q64",
+    "psk31_sync", "psk31_sync_batch", "best_psk31_sync", "psk31_decode", "psk31_decode_batch", "Psk31Stream",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -194,6 +199,50 @@ def _load():
         "orion_ft_demod": (i, [i, f, f, vp, sz, sz, vp, vp]),
         "orion_ft_demod_device": (i, [i, f, f, vp, sz, sz, vp, vp, vp]),
         "orion_ft_demod_host": (i, [i, f, f, vp, vp, vp]),
+        "orion_psk31_tables": (i, [vp, vp, vp]),
+        "orion_varicode_encode": (i, [C.c_uint8, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+        "orion_varicode_decode": (i, [C.c_uint16, C.c_uint8]),
+        "orion_varicode_encoder_new": (vp, []), "orion_varicode_encoder_free": (None, [vp]),
+        "orion_varicode_encoder_push_preamble": (i, [vp, sz]), "orion_varicode_encoder_push_byte": (i, [vp, C.c_uint8]),
+        "orion_varicode_encoder_push_postamble": (i, [vp, sz]), "orion_varicode_encoder_pending": (sz, [vp]),
+        "orion_varicode_encoder_drain": (i, [vp, vp, sz, C.POINTER(sz)]),
+        "orion_varicode_decoder_new": (vp, []), "orion_varicode_decoder_free": (None, [vp]),
+        "orion_varicode_decoder_push_bits": (i, [vp, vp, sz]), "orion_varicode_decoder_pending": (sz, [vp]),
+        "orion_varicode_decoder_pop_bytes": (i, [vp, vp, sz, C.POINTER(sz)]),
+        "orion_conv_encode": (i, [vp, sz, vp]),
+        "orion_psk31_viterbi": (i, [vp, sz, sz, vp]),
+        "orion_psk31_viterbi_device": (i, [vp, sz, sz, vp, vp, sz, vp]),
+        "orion_psk31_viterbi_work_bytes": (sz, [sz, sz]),
+        "orion_psk31_viterbi_host": (i, [vp, sz, vp]), "orion_psk31_viterbi_hard_host": (i, [vp, sz, vp]),
+        "orion_psk31_streaming_viterbi_new": (vp, []), "orion_psk31_streaming_viterbi_free": (None, [vp]),
+        "orion_psk31_streaming_viterbi_feed": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "orion_psk31_streaming_viterbi_flush": (i, [vp, vp, C.POINTER(sz)]),
+        "orion_psk31_sps": (sz, [f]),
+        "orion_psk31_synth": (i, [f, vp, vp, sz, sz, sz, i, vp]),
+        "orion_psk31_synth_device": (i, [f, vp, vp, sz, sz, sz, i, vp, vp]),
+        "orion_psk31_rotator_q64": (C.c_uint64, [f, f]),
+        "orion_psk31_text_bits": (i, [vp, sz, sz, sz, vp, sz, C.POINTER(sz)]),
+        "orion_psk31_mod_new": (vp, [i, f, f, f]), "orion_psk31_mod_free": (None, [vp]),
+        "orion_psk31_mod_set_gain": (i, [vp, f]), "orion_psk31_mod_reset": (i, [vp]),
+        "orion_psk31_mod_modulate_bits": (i, [vp, vp, sz, vp]),
+        "orion_psk31_mod_modulate_bits_device": (i, [vp, vp, sz, vp, vp]),
+        "orion_psk31_mod_modulate_batch": (i, [vp, vp, sz, sz, vp]),
+        "orion_psk31_mod_modulate_batch_device": (i, [vp, vp, sz, sz, vp, vp]),
+        "orion_psk31_mod_process": (i, [vp, vp, sz, vp, sz, C.POINTER(WorkReport)]),
+        "orion_psk31_demod_new": (vp, [i, f, f, f, sz]), "orion_psk31_demod_free": (None, [vp]),
+        "orion_psk31_demod_set_gain": (i, [vp, f]), "orion_psk31_demod_reset": (i, [vp]),
+        "orion_psk31_demod_process": (i, [vp, vp, sz, vp, sz, C.POINTER(WorkReport)]),
+        "orion_bpsk31_decide": (i, [vp, sz, vp]),
+        "orion_psk31_demod_bank_new": (vp, [f, vp, sz, sz]), "orion_psk31_demod_bank_free": (None, [vp]),
+        "orion_psk31_demod_bank_process": (i, [vp, vp, sz, sz, vp, sz, vp, vp]),
+        "orion_psk31_demod_bank_process_device": (i, [vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "orion_psk31_demod_bank_reset": (i, [vp]), "orion_psk31_demod_bank_set_gain": (i, [vp, sz, f]),
+        "orion_psk31_find_carriers_host": (i, [vp, sz, sz, sz, sz, f, sz, vp, vp]),
+        "orion_psk31_sync_num_bins": (sz, [f, f]),
+        "orion_psk31_find_carriers": (i, [vp, vp, sz, sz, sz, sz, f, sz, vp, vp]),
+        "orion_psk31_find_carriers_device": (i, [vp, vp, sz, sz, sz, sz, f, sz, vp, vp, vp]),
+        "orion_psk31_sync": (i, [vp, vp, sz, sz, f, f, f, sz, f, sz, sz, vp, vp, vp, vp]),
+        "orion_psk31_sync_device": (i, [vp, vp, sz, sz, f, f, f, sz, f, sz, sz, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1581,6 +1630,742 @@ def ft8_synth(signals, tones, n, nch=1, fs=12000.0, out=None, accumulate=False, 
 def ft4_synth(signals, tones, n, nch=1, fs=12000.0, out=None, accumulate=False, device=False, stream=None):
     """ft8_synth for FT4 frames: tones uint8 (nsig, 87)."""
     return _ft_synth("ft4", signals, tones, n, nch, fs, out, accumulate, device, stream)
+
+
+# ---- PSK31 channel code: Varicode and QPSK31's rate 1/2, K = 5 code (src/codec) -------------
+VARICODE_MAX_BITS = 10
+PSK31_TRACEBACK_DEPTH = 32
+
+
+def _bits_arg(bits, what="bits") -> np.ndarray:
+    if not isinstance(bits, np.ndarray) or bits.dtype != np.uint8 or bits.ndim != 1:
+        raise ValueError(f"{what}: expected a 1-D uint8 array")
+    return np.ascontiguousarray(bits)
+
+
+def _soft_arg(soft, batched) -> np.ndarray:
+    if not isinstance(soft, np.ndarray) or soft.dtype != np.float32 or soft.ndim != (2 if batched else 1):
+        raise ValueError(f"soft: expected a {'2' if batched else '1'}-D float32 array")
+    if soft.shape[-1] % 2:
+        raise ValueError("soft: an interleaved (re, im) pair per symbol, so an even length")
+    return np.ascontiguousarray(soft)
+
+
+def psk31_tables():
+    """Host only: (varicode codewords uint16 (128,), MSB first; their lengths uint8 (128,);
+    DQPSK_EXP float32 (4, 2)) as the library holds them (varicode.rs:27-156, psk31.rs:80-85)."""
+    cw = np.zeros(128, np.uint16)
+    ln = np.zeros(128, np.uint8)
+    exp = np.zeros((4, 2), np.float32)
+    _check(_L.orion_psk31_tables(cw.ctypes.data, ln.ctypes.data, exp.ctypes.data))
+    return cw, ln, exp
+
+
+def varicode_encode(byte: int):
+    """varicode_encode (varicode.rs:163-169): (codeword, length); a byte >= 128 gives NUL's."""
+    if not 0 <= int(byte) <= 255:
+        raise ValueError("byte out of range")
+    cw, ln = C.c_uint16(0), C.c_uint8(0)
+    _check(_L.orion_varicode_encode(int(byte), C.byref(cw), C.byref(ln)))
+    return cw.value, ln.value
+
+
+def varicode_decode(bits: int, length: int):
+    """varicode_decode (varicode.rs:176-183): the byte, or None for an unknown codeword."""
+    if not (0 <= int(bits) <= 0xFFFF and 0 <= int(length) <= 255):
+        raise ValueError("codeword out of range")
+    r = _L.orion_varicode_decode(int(bits), int(length))
+    return None if r < 0 else int(r)
+
+
+class VaricodeEncoder:
+    """VaricodeEncoder (varicode.rs:192-267; __init__.pyi:459-475), host only."""
+
+    def __init__(self):
+        self._h = _L.orion_varicode_encoder_new()
+        if not self._h:
+            raise OrionError(f"orion_sdr: {_err()}")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_varicode_encoder_free(h)
+
+    @staticmethod
+    def _count(n) -> int:
+        if int(n) < 0:
+            raise ValueError("a bit count is not negative")
+        return int(n)
+
+    def push_preamble(self, n: int) -> None:
+        rc = _L.orion_varicode_encoder_push_preamble(self._h, self._count(n))
+        if rc == -3:
+            raise ValueError(_err())
+        _check(rc)
+
+    def push_byte(self, b: int) -> None:
+        if not 0 <= int(b) <= 255:
+            raise ValueError("byte out of range")
+        _check(_L.orion_varicode_encoder_push_byte(self._h, int(b)))
+
+    def push_postamble(self, n: int) -> None:
+        rc = _L.orion_varicode_encoder_push_postamble(self._h, self._count(n))
+        if rc == -3:
+            raise ValueError(_err())
+        _check(rc)
+
+    def drain_bits(self) -> np.ndarray:
+        out = np.zeros(_L.orion_varicode_encoder_pending(self._h), np.uint8)
+        n = C.c_size_t(0)
+        _check(_L.orion_varicode_encoder_drain(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value]
+
+    def is_empty(self) -> bool:
+        return _L.orion_varicode_encoder_pending(self._h) == 0
+
+
+class VaricodeDecoder:
+    """VaricodeDecoder (varicode.rs:277-320; __init__.pyi:477-486), host only."""
+
+    def __init__(self):
+        self._h = _L.orion_varicode_decoder_new()
+        if not self._h:
+            raise OrionError(f"orion_sdr: {_err()}")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_varicode_decoder_free(h)
+
+    def push_bits(self, bits) -> None:
+        bits = _bits_arg(bits)
+        _check(_L.orion_varicode_decoder_push_bits(self._h, bits.ctypes.data, bits.size))
+
+    def pop_bytes(self) -> bytes:
+        out = np.zeros(_L.orion_varicode_decoder_pending(self._h), np.uint8)
+        n = C.c_size_t(0)
+        _check(_L.orion_varicode_decoder_pop_bytes(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value].tobytes()
+
+
+def conv_encode(bits) -> np.ndarray:
+    """conv_encode (psk31.rs:45-55): uint8 bits (n,) -> coded bits (2 n,), host only."""
+    bits = _bits_arg(bits)
+    out = np.zeros(2 * bits.size, np.uint8)
+    _check(_L.orion_conv_encode(bits.ctypes.data, bits.size, out.ctypes.data))
+    return out
+
+
+def viterbi_decode(soft) -> np.ndarray:
+    """viterbi_decode (psk31.rs:95-160) by the library's scalar decoder (host only; what the
+    kernel is held to): float32 (2 n_syms,) -> uint8 bits (n_syms,)."""
+    soft = _soft_arg(soft, False)
+    out = np.zeros(soft.size // 2, np.uint8)
+    _check(_L.orion_psk31_viterbi_host(soft.ctypes.data, out.size, out.ctypes.data))
+    return out
+
+
+def viterbi_decode_hard(coded) -> np.ndarray:
+    """viterbi_decode_hard (psk31.rs:384-396): coded bits (2 n_syms,) -> bits (n_syms,), host only."""
+    coded = _bits_arg(coded, "coded")
+    if coded.size % 2:
+        raise ValueError("coded: two bits per symbol, so an even length")
+    out = np.zeros(coded.size // 2, np.uint8)
+    _check(_L.orion_psk31_viterbi_hard_host(coded.ctypes.data, out.size, out.ctypes.data))
+    return out
+
+
+def psk31_viterbi_batch(soft, stream=None):
+    """viterbi_decode of a batch of soft streams on the GPU in one launch (sixteen lanes per
+    stream, four streams per wave): float32 (nstreams, 2 n_syms), a numpy array (-> numpy
+    uint8 (nstreams, n_syms)) or a contiguous torch CUDA tensor (-> a torch uint8 tensor on
+    its device, queued on torch's current stream or on stream)."""
+    if _is_torch(soft):
+        import torch
+
+        if not soft.is_cuda or not soft.is_contiguous() or soft.dtype != torch.float32 or soft.dim() != 2:
+            raise ValueError("psk31_viterbi_batch needs a contiguous 2-D float32 CUDA tensor")
+        if soft.shape[1] % 2:
+            raise ValueError("soft: an interleaved (re, im) pair per symbol, so an even length")
+        ns, n = int(soft.shape[0]), int(soft.shape[1]) // 2
+        bits = torch.empty((ns, n), dtype=torch.uint8, device=soft.device)
+        wb = int(_L.orion_psk31_viterbi_work_bytes(ns, n))
+        work = torch.empty(max(wb // 4, 1), dtype=torch.int32, device=soft.device)
+        rc = _L.orion_psk31_viterbi_device(soft.data_ptr(), ns, n, bits.data_ptr(), work.data_ptr(), wb,
+                                           SyncEngine._stream(soft, stream))
+        if rc == -3:
+            raise ValueError(_err())
+        _check(rc)
+        return bits
+    soft = _soft_arg(soft, True)
+    ns, n = soft.shape[0], soft.shape[1] // 2
+    bits = np.zeros((ns, n), np.uint8)
+    rc = _L.orion_psk31_viterbi(soft.ctypes.data, ns, n, bits.ctypes.data)
+    if rc == -3:
+        raise ValueError(_err())
+    _check(rc)
+    return bits
+
+
+class StreamingViterbi:
+    """StreamingViterbi (psk31.rs:257-377) on DQPSK_EXP, host only: feed(float32 (2 n,)) ->
+    the bits that come out (none for a decoder's first 32 symbols), flush() -> the last 32."""
+
+    def __init__(self):
+        self._h = _L.orion_psk31_streaming_viterbi_new()
+        if not self._h:
+            raise OrionError(f"orion_sdr: {_err()}")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_psk31_streaming_viterbi_free(h)
+
+    def feed(self, soft) -> np.ndarray:
+        soft = _soft_arg(soft, False)
+        out = np.zeros(soft.size // 2, np.uint8)
+        n = C.c_size_t(0)
+        _check(_L.orion_psk31_streaming_viterbi_feed(self._h, soft.ctypes.data, out.size, out.ctypes.data, C.byref(n)))
+        return out[:n.value]
+
+    def flush(self) -> np.ndarray:
+        out = np.zeros(PSK31_TRACEBACK_DEPTH, np.uint8)
+        n = C.c_size_t(0)
+        _check(_L.orion_psk31_streaming_viterbi_flush(self._h, out.ctypes.data, C.byref(n)))
+        return out[:n.value]
+
+
+# ---- PSK31 modulators and demodulators (src/modulate/psk31.rs, src/demodulate/psk31.rs) -------
+PSK31_STREAM_DTYPE = np.dtype([("mode", np.uint32), ("channel", np.uint32), ("rf_hz", np.float32), ("gain", np.float32),
+                               ("start", np.uint64), ("offset", np.uint32), ("out_cap", np.uint32)])
+PSK31_REPORT_DTYPE = np.dtype([("in_read", np.uint64), ("out_written", np.uint64)])
+_PSK31_MODES = {"bpsk": 0, "qpsk": 1, 0: 0, 1: 1}
+
+
+def _arg_check(rc: int):
+    if rc == -3:
+        raise ValueError(_err())
+    _check(rc)
+
+
+def _iq_arg(iq, ndim=1) -> np.ndarray:
+    if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != ndim:
+        raise ValueError(f"iq: expected a {ndim}-D complex64 array")
+    return np.ascontiguousarray(iq)
+
+
+def psk31_sps(fs: float) -> int:
+    """psk31_sps (modulate/psk31.rs:42-44): round(fs / 31.25) samples per symbol."""
+    return int(_L.orion_psk31_sps(float(fs)))
+
+
+def psk31_text_bits(text, preamble_bits: int = 32, postamble_bits: int = 32) -> np.ndarray:
+    """The bits modulate_text sends (modulate/psk31.rs:146-159), host only."""
+    text = bytes(text)
+    if int(preamble_bits) < 0 or int(postamble_bits) < 0:
+        raise ValueError("a bit count is not negative")
+    n = C.c_size_t(0)
+    rc = _L.orion_psk31_text_bits(text, len(text), int(preamble_bits), int(postamble_bits), None, 0, C.byref(n))
+    if rc == -3 and n.value == 0:
+        raise ValueError(_err())
+    out = np.zeros(n.value, np.uint8)
+    _arg_check(_L.orion_psk31_text_bits(text, len(text), int(preamble_bits), int(postamble_bits), out.ctypes.data, out.size,
+                                        C.byref(n)))
+    return out
+
+
+class _Psk31Mod:
+    """Bpsk31Mod / Qpsk31Mod (modulate/psk31.rs:110-216, :248-362; __init__.pyi:492-544): the
+    library's host modulator in the reference's f32 operation order. The phasor (and
+    QPSK31's coder register) is kept between calls; reset() returns to the start."""
+    _mode = 0
+
+    def __init__(self, fs: float, rf_hz: float, gain: float = 1.0):
+        self._h = _L.orion_psk31_mod_new(self._mode, float(fs), float(rf_hz), float(gain))
+        if not self._h:
+            raise ValueError(f"orion_sdr: {_err()}")
+        self.sps = psk31_sps(fs)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_psk31_mod_free(h)
+
+    def set_gain(self, g: float) -> None:
+        _check(_L.orion_psk31_mod_set_gain(self._h, float(g)))
+
+    def reset(self) -> None:
+        _check(_L.orion_psk31_mod_reset(self._h))
+
+    def modulate_bits(self, bits, device=False, stream=None):
+        """bits uint8 (n,) -> iq complex64 (n * sps,): a numpy array from the host modulator, or
+        with device=True a torch tensor on the current device from the kernel (the same bytes;
+        the state advances either way)."""
+        bits = _bits_arg(bits)
+        if device:
+            import torch
+
+            out = torch.empty(bits.size * self.sps, dtype=torch.complex64, device="cuda")
+            _arg_check(_L.orion_psk31_mod_modulate_bits_device(self._h, bits.ctypes.data, bits.size, out.data_ptr(),
+                                                               SyncEngine._stream(out, stream)))
+            return out
+        out = np.zeros(bits.size * self.sps, np.complex64)
+        _check(_L.orion_psk31_mod_modulate_bits(self._h, bits.ctypes.data, bits.size, out.ctypes.data))
+        return out
+
+    def modulate_batch(self, bits, device=False, stream=None):
+        """bits uint8 (nstreams, n) -> iq complex64 (nstreams, n * sps) by one kernel launch,
+        every stream from a fresh modulator of these parameters (this one's state is not
+        touched): numpy, or with device=True a torch tensor."""
+        if not isinstance(bits, np.ndarray) or bits.dtype != np.uint8 or bits.ndim != 2:
+            raise ValueError("bits: expected a 2-D uint8 array")
+        bits = np.ascontiguousarray(bits)
+        ns, n = bits.shape
+        if device:
+            import torch
+
+            out = torch.empty((ns, n * self.sps), dtype=torch.complex64, device="cuda")
+            _arg_check(_L.orion_psk31_mod_modulate_batch_device(self._h, bits.ctypes.data, ns, n, out.data_ptr(),
+                                                                SyncEngine._stream(out, stream)))
+            return out
+        out = np.zeros((ns, n * self.sps), np.complex64)
+        _arg_check(_L.orion_psk31_mod_modulate_batch(self._h, bits.ctypes.data, ns, n, out.ctypes.data))
+        return out
+
+    def modulate_text(self, text, preamble_bits: int = 32, postamble_bits: int = 32, device=False):
+        return self.modulate_bits(psk31_text_bits(text, preamble_bits, postamble_bits), device=device)
+
+    def process(self, bits, out_cap: int):
+        """Block::process (:199-215): -> (iq written, bits read)."""
+        bits = _bits_arg(bits)
+        out = np.zeros(int(out_cap), np.complex64)
+        wr = WorkReport()
+        _check(_L.orion_psk31_mod_process(self._h, bits.ctypes.data, bits.size, out.ctypes.data, out.size, C.byref(wr)))
+        return out[:wr.out_written], int(wr.in_read)
+
+
+class Bpsk31Mod(_Psk31Mod):
+    _mode = 0
+
+
+class Qpsk31Mod(_Psk31Mod):
+    _mode = 1
+
+
+class Psk31DemodBank:
+    """nstreams independent BPSK31 / QPSK31 demodulators over nch channels, advanced by one
+    kernel launch per call (one lane per stream). records: a PSK31_STREAM_DTYPE array (mode 0
+    BPSK / 1 QPSK, channel, rf_hz, gain, start sample, offset as new_with_offset, out_cap soft
+    values per call). process(iq (nch, n) complex64) -> (soft float32 (nstreams, out_stride),
+    bits uint8 the same shape (soft >= 0 for BPSK31 streams, zeros for QPSK31 streams, whose
+    decisions are the Viterbi decoder's), reports PSK31_REPORT_DTYPE (nstreams,)); row k
+    holds out_written[k] values. numpy in, numpy out; a torch CUDA tensor in, torch tensors
+    out (reports as an int64 (nstreams, 2) tensor) on torch's current stream. State is carried
+    between calls: chunked calls give one call's bytes."""
+
+    def __init__(self, fs: float, records, nch: int = 1):
+        if not isinstance(records, np.ndarray) or records.dtype != PSK31_STREAM_DTYPE or records.ndim != 1:
+            raise ValueError("records: expected a 1-D PSK31_STREAM_DTYPE array")
+        records = np.ascontiguousarray(records)
+        self._h = _L.orion_psk31_demod_bank_new(float(fs), records.ctypes.data, records.size, int(nch))
+        if not self._h:
+            raise ValueError(f"orion_sdr: {_err()}")
+        self.nstreams, self.nch = int(records.size), int(nch)
+        self.out_stride = max(int(records["out_cap"].max()), 1)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_psk31_demod_bank_free(h)
+
+    def reset(self) -> None:
+        _check(_L.orion_psk31_demod_bank_reset(self._h))
+
+    def set_gain(self, index: int, gain: float) -> None:
+        _arg_check(_L.orion_psk31_demod_bank_set_gain(self._h, int(index), float(gain)))
+
+    def process(self, iq, want_bits=True, stream=None):
+        if _is_torch(iq):
+            import torch
+
+            if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+                raise ValueError("Psk31DemodBank.process needs a contiguous (nch, n) complex64 CUDA tensor")
+            soft = torch.zeros((self.nstreams, self.out_stride), dtype=torch.float32, device=iq.device)
+            bits = torch.zeros((self.nstreams, self.out_stride), dtype=torch.uint8, device=iq.device) if want_bits else None
+            rep = torch.zeros((self.nstreams, 2), dtype=torch.int64, device=iq.device)
+            _arg_check(_L.orion_psk31_demod_bank_process_device(
+                self._h, iq.data_ptr(), int(iq.shape[0]), int(iq.shape[1]), soft.data_ptr(), self.out_stride,
+                bits.data_ptr() if want_bits else None, rep.data_ptr(), SyncEngine._stream(iq, stream)))
+            return soft, bits, rep
+        return self.process_host(iq, want_bits)
+
+    def process_host(self, iq, want_bits=True):
+        iq = _iq_arg(iq, 2)
+        soft = np.zeros((self.nstreams, self.out_stride), np.float32)
+        bits = np.zeros((self.nstreams, self.out_stride), np.uint8) if want_bits else None
+        rep = np.zeros(self.nstreams, PSK31_REPORT_DTYPE)
+        _arg_check(_L.orion_psk31_demod_bank_process(self._h, iq.ctypes.data, iq.shape[0], iq.shape[1], soft.ctypes.data,
+                                                     self.out_stride, bits.ctypes.data if want_bits else None,
+                                                     rep.ctypes.data))
+        return soft, bits, rep
+
+
+class _Psk31Demod:
+    """Bpsk31Demod / Qpsk31Demod (demodulate/psk31.rs:83-220, :271-397; __init__.pyi:510-561).
+    process runs on the GPU, as a bank of one stream (one lane: the chain is serial in time, so
+    a single stream is slower there than on the host; the bank is for many). process_host is
+    the library's scalar demodulator, the reference's arithmetic with glibc's sine and cosine;
+    the two keep separate state."""
+    _mode = 0
+
+    def __init__(self, fs: float, rf_hz: float, gain: float = 1.0, offset: int = 0):
+        if int(offset) < 0:
+            raise ValueError("offset is not negative")
+        self._fs, self._rf, self._gain, self._offset = float(fs), float(rf_hz), float(gain), int(offset)
+        self._h = _L.orion_psk31_demod_new(self._mode, self._fs, self._rf, self._gain, self._offset)
+        if not self._h:
+            raise ValueError(f"orion_sdr: {_err()}")
+        self.sps = psk31_sps(fs)
+        self._bank = None
+        self._bank_cap = 0
+        self._soft = []
+
+    @classmethod
+    def new_with_offset(cls, fs: float, rf_hz: float, gain: float, offset: int):
+        return cls(fs, rf_hz, gain, offset)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _L is not None:
+            _L.orion_psk31_demod_free(h)
+
+    def set_gain(self, g: float) -> None:
+        self._gain = float(g)
+        _check(_L.orion_psk31_demod_set_gain(self._h, self._gain))
+        if self._bank is not None:
+            self._bank.set_gain(0, self._gain)
+
+    def reset(self) -> None:
+        _check(_L.orion_psk31_demod_reset(self._h))
+        if self._bank is not None:
+            self._bank.reset()
+        self._soft = []
+
+    def _cap(self, n: int) -> int:
+        return (n // self.sps + 2) * (2 if self._mode else 1)
+
+    _BANK_CAP = 4096  # soft values per bank call; longer inputs go through in slices
+
+    def process(self, iq) -> np.ndarray:
+        iq = _iq_arg(iq)
+        if self._bank is None:
+            rec = np.zeros(1, PSK31_STREAM_DTYPE)
+            rec[0] = (self._mode, 0, self._rf, self._gain, 0, self._offset, self._BANK_CAP)
+            self._bank = Psk31DemodBank(self._fs, rec, 1)
+        step = (self._BANK_CAP // 2 - 2) * self.sps  # a slice never fills the capacity, so none is cut short
+        parts = []
+        for at in range(0, iq.size, step):
+            soft, _, rep = self._bank.process_host(iq[at:at + step].reshape(1, -1), want_bits=False)
+            parts.append(soft[0, :int(rep["out_written"][0])].copy())
+        out = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+        self._soft.append(out)
+        return out
+
+    def process_host(self, iq, out_cap=None):
+        """-> (soft, in_read) by the scalar host demodulator, with the reference's loop
+        conditions for an output of out_cap values (default: room for every symbol)."""
+        iq = _iq_arg(iq)
+        out = np.zeros(self._cap(iq.size) if out_cap is None else int(out_cap), np.float32)
+        wr = WorkReport()
+        _check(_L.orion_psk31_demod_process(self._h, iq.ctypes.data, iq.size, out.ctypes.data, out.size, C.byref(wr)))
+        return out[:wr.out_written].copy(), int(wr.in_read)
+
+
+class Bpsk31Demod(_Psk31Demod):
+    _mode = 0
+
+
+class Qpsk31Demod(_Psk31Demod):
+    _mode = 1
+
+    def flush(self) -> np.ndarray:
+        """Qpsk31Decider::flush (demodulate/psk31.rs:422-428): the Viterbi decode (on the GPU)
+        of every soft pair process() has returned since the last flush."""
+        soft = np.concatenate(self._soft) if self._soft else np.zeros(0, np.float32)
+        self._soft = []
+        if soft.size == 0:
+            return np.zeros(0, np.uint8)
+        return psk31_viterbi_batch(soft.reshape(1, -1))[0]
+
+
+class Bpsk31Decider:
+    """Bpsk31Decider (demodulate/psk31.rs:228-261): bit = soft >= 0, host only."""
+
+    def process(self, soft) -> np.ndarray:
+        if not isinstance(soft, np.ndarray) or soft.dtype != np.float32 or soft.ndim != 1:
+            raise ValueError("soft: expected a 1-D float32 array")
+        soft = np.ascontiguousarray(soft)
+        out = np.zeros(soft.size, np.uint8)
+        _check(_L.orion_bpsk31_decide(soft.ctypes.data, soft.size, out.ctypes.data))
+        return out
+
+
+PSK31_SIGNAL_DTYPE = np.dtype([("channel", np.uint32), ("mode", np.uint32), ("offset", np.int64), ("rf_hz", np.float32),
+                               ("gain", np.float32), ("n_bits", np.uint64)])
+
+
+def psk31_rotator_q64(freq_hz: float, fs: float) -> int:
+    """The angle of Rotator(freq_hz, fs)'s f32 step phasor as a Q0.64 turn count (host only):
+    what psk31_synth's RF stage is the closed form of."""
+    return int(_L.orion_psk31_rotator_q64(float(freq_hz), float(fs)))
+
+
+def psk31_synth(signals, bits, n, nch=1, fs=8000.0, out=None, accumulate=False, device=False, stream=None):
+    """Many PSK31 signals summed into many channels in one launch: signals a
+    PSK31_SIGNAL_DTYPE array (channel, mode 0 BPSK / 1 QPSK, offset, rf_hz, gain; n_bits is
+    filled in here), bits a list of uint8 arrays, one per signal -> iq complex64 (nch, n).
+    out + accumulate=True adds to an existing buffer. numpy, or with device=True a torch
+    tensor (out must then be a CUDA tensor if given)."""
+    if not isinstance(signals, np.ndarray) or signals.dtype != PSK31_SIGNAL_DTYPE or signals.ndim != 1:
+        raise ValueError("signals: expected a 1-D PSK31_SIGNAL_DTYPE array")
+    if len(bits) != signals.size:
+        raise ValueError("bits: one uint8 array per signal")
+    rows = [_bits_arg(b) for b in bits]
+    sig = np.ascontiguousarray(signals).copy()
+    sig["n_bits"] = [r.size for r in rows]
+    allbits = np.ascontiguousarray(np.concatenate(rows)) if rows and sum(r.size for r in rows) else np.zeros(1, np.uint8)
+    n, nch = int(n), int(nch)
+    if n < 0 or nch < 1:
+        raise ValueError("n >= 0 and nch >= 1")
+    if device or (out is not None and _is_torch(out)):
+        import torch
+
+        if out is None:
+            out = torch.zeros((nch, n), dtype=torch.complex64, device="cuda")
+        elif not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.complex64
+                  and tuple(out.shape) == (nch, n)):
+            raise ValueError("out: a contiguous (nch, n) complex64 CUDA tensor")
+        _arg_check(_L.orion_psk31_synth_device(float(fs), sig.ctypes.data, allbits.ctypes.data, sig.size, nch, n,
+                                               1 if accumulate else 0, out.data_ptr(), SyncEngine._stream(out, stream)))
+        return out
+    if out is None:
+        out = np.zeros((nch, n), np.complex64)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.complex64 and out.shape == (nch, n) and out.flags.c_contiguous):
+        raise ValueError("out: a C-contiguous (nch, n) complex64 array")
+    _arg_check(_L.orion_psk31_synth(float(fs), sig.ctypes.data, allbits.ctypes.data, sig.size, nch, n, 1 if accumulate else 0,
+                                    out.ctypes.data))
+    return out
+
+
+# ---- PSK31 carrier search, sync and the band browser (src/sync/psk31_sync.rs) ----------------
+PSK31_BAUD = 31.25
+
+
+def psk31_find_carriers(wf, min_carrier_syms: int = 8, peak_margin_db: float = 6.0, max_cand: int = 10):
+    """The search of psk31_sync (psk31_sync.rs:82-203) over a log waterfall, on the host: wf
+    float32 (num_syms, num_bins) -> a CANDIDATE_DTYPE array, score descending (equal scores
+    by freq_bin, then time_sym), or (nch, num_syms, num_bins) -> a list of them."""
+    if not isinstance(wf, np.ndarray) or wf.dtype != np.float32 or wf.ndim not in (2, 3):
+        raise ValueError("wf: expected a 2-D or 3-D float32 array")
+    if int(max_cand) < 1:
+        raise ValueError("max_cand == 0")
+    if int(min_carrier_syms) < 0:
+        raise ValueError("min_carrier_syms is not negative")
+    w3 = np.ascontiguousarray(wf if wf.ndim == 3 else wf[None])
+    nch = w3.shape[0]
+    cand = np.zeros((nch, int(max_cand)), CANDIDATE_DTYPE)
+    count = np.zeros(nch, np.uint32)
+    _arg_check(_L.orion_psk31_find_carriers_host(w3.ctypes.data, nch, w3.shape[1], w3.shape[2], int(min_carrier_syms),
+                                                 float(peak_margin_db), int(max_cand), cand.ctypes.data,
+                                                 count.ctypes.data))
+    out = [cand[ch, :count[ch]].copy() for ch in range(nch)]
+    return out if wf.ndim == 3 else out[0]
+
+
+def psk31_find_carriers_device(wf, min_carrier_syms: int = 8, peak_margin_db: float = 6.0, max_cand: int = 10,
+                                stream=None):
+    """The same search by the device kernels (orion_psk31_find_carriers / _device): wf float32
+    (num_syms, num_bins) or (nch, num_syms, num_bins), a numpy array or a contiguous torch CUDA
+    tensor. -> as psk31_find_carriers (numpy either way); equal to it, order and scores
+    included."""
+    tw = _is_torch(wf)
+    if tw:
+        import torch
+
+        if not wf.is_cuda or not wf.is_contiguous() or wf.dtype != torch.float32 or wf.dim() not in (2, 3):
+            raise ValueError("wf: expected a contiguous 2-D or 3-D float32 CUDA tensor")
+    elif not isinstance(wf, np.ndarray) or wf.dtype != np.float32 or wf.ndim not in (2, 3):
+        raise ValueError("wf: expected a 2-D or 3-D float32 array")
+    if int(max_cand) < 1:
+        raise ValueError("max_cand == 0")
+    if int(min_carrier_syms) < 0:
+        raise ValueError("min_carrier_syms is not negative")
+    three = len(wf.shape) == 3
+    nch, num_syms, num_bins = (int(v) for v in (wf.shape if three else (1,) + tuple(wf.shape)))
+    eng = _sync_engine()
+    if tw:
+        import torch
+
+        cand = torch.zeros((nch, int(max_cand), 3), dtype=torch.int32, device=wf.device)
+        count = torch.zeros(nch, dtype=torch.int32, device=wf.device)
+        _arg_check(_L.orion_psk31_find_carriers_device(eng._h, wf.data_ptr(), nch, num_syms, num_bins,
+                                                       int(min_carrier_syms), float(peak_margin_db), int(max_cand),
+                                                       cand.data_ptr(), count.data_ptr(), SyncEngine._stream(wf, stream)))
+        hc = cand.cpu().numpy().view(CANDIDATE_DTYPE)[..., 0]
+        hn = count.cpu().numpy().view(np.uint32)
+    else:
+        w3 = np.ascontiguousarray(wf)
+        hc = np.zeros((nch, int(max_cand)), CANDIDATE_DTYPE)
+        hn = np.zeros(nch, np.uint32)
+        _arg_check(_L.orion_psk31_find_carriers(eng._h, w3.ctypes.data, nch, num_syms, num_bins, int(min_carrier_syms),
+                                                float(peak_margin_db), int(max_cand), hc.ctypes.data, hn.ctypes.data))
+    out = [hc[ch, :hn[ch]].copy() for ch in range(nch)]
+    return out if three else out[0]
+
+
+def psk31_sync_batch(iq, fs, base_hz, max_hz, min_carrier_syms=8, peak_margin_db=6.0, n_bits=1024, max_cand=10,
+                     stream=None):
+    """psk31_sync (psk31_sync.rs:50-205) for every row of iq (nch, n) complex64, one device
+    call with no trip to the host between its stages (orion_psk31_sync / _device): the
+    waterfall (one bin per 31.25 Hz), the carrier search, the candidates' bank records
+    written on the device, and every kept candidate's soft bits from one launch of the
+    demodulator bank (record_candidate, :209-239: a BPSK31 stream at base_hz + freq_bin *
+    31.25 from sample time_sym * sps, gain 1, capacity n_bits + 2, the first min(out_written,
+    n_bits) values). iq: a numpy array (uploaded once) or a contiguous torch CUDA tensor (it
+    stays where it is). -> per channel a list of dicts time_sym, freq_bin, carrier_hz, score,
+    soft_bits (numpy)."""
+    ti = _is_torch(iq)
+    if ti:
+        import torch
+
+        if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+            raise ValueError("psk31_sync_batch needs a contiguous (nch, n) complex64 CUDA tensor")
+    else:
+        iq = _iq_arg(iq, 2)
+    if int(max_cand) < 1:
+        raise ValueError("max_cand == 0")
+    if int(n_bits) < 0 or int(n_bits) > (1 << 30) - 2:
+        raise ValueError("n_bits out of range")
+    if int(min_carrier_syms) < 0:
+        raise ValueError("min_carrier_syms is not negative")
+    nch, n = int(iq.shape[0]), int(iq.shape[1])
+    sps = psk31_sps(fs)
+    if sps == 0 or n // sps == 0:
+        return [[] for _ in range(nch)]
+    mc, nb = int(max_cand), int(n_bits)
+    args = (nch, n, float(fs), float(base_hz), float(max_hz), int(min_carrier_syms), float(peak_margin_db), nb, mc)
+    eng = _sync_engine()
+    if ti:
+        import torch
+
+        cand = torch.zeros((nch, mc, 3), dtype=torch.int32, device=iq.device)
+        count = torch.zeros(nch, dtype=torch.int32, device=iq.device)
+        soft = torch.zeros((nch, mc, nb + 2), dtype=torch.float32, device=iq.device)
+        rep = torch.zeros((nch, mc, 2), dtype=torch.int64, device=iq.device)
+        _arg_check(_L.orion_psk31_sync_device(eng._h, iq.data_ptr(), *args, cand.data_ptr(), count.data_ptr(),
+                                              soft.data_ptr(), rep.data_ptr(), SyncEngine._stream(iq, stream)))
+        cand = cand.cpu().numpy().view(CANDIDATE_DTYPE)[..., 0]
+        count = count.cpu().numpy().view(np.uint32)
+        soft, rep = soft.cpu().numpy(), rep.cpu().numpy()
+    else:
+        cand = np.zeros((nch, mc), CANDIDATE_DTYPE)
+        count = np.zeros(nch, np.uint32)
+        soft = np.zeros((nch, mc, nb + 2), np.float32)
+        rep = np.zeros((nch, mc, 2), np.int64)
+        _arg_check(_L.orion_psk31_sync(eng._h, iq.ctypes.data, *args, cand.ctypes.data, count.ctypes.data,
+                                       soft.ctypes.data, rep.ctypes.data))
+    out = []
+    for ch in range(nch):
+        row = []
+        for k in range(int(count[ch])):
+            c = cand[ch, k]
+            carrier = float(np.float32(base_hz) + np.float32(c["freq_bin"]) * np.float32(PSK31_BAUD))
+            keep = min(int(rep[ch, k, 1]), nb)
+            row.append({"time_sym": int(c["time_sym"]), "freq_bin": int(c["freq_bin"]), "carrier_hz": carrier,
+                        "score": float(c["score"]), "soft_bits": soft[ch, k, :keep].copy()})
+        out.append(row)
+    return out
+
+
+def psk31_sync(iq, fs, base_hz, max_hz, min_carrier_syms=8, peak_margin_db=6.0, n_bits=1024, max_cand=10):
+    """psk31_sync (__init__.pyi:591-613) of one buffer: a list of candidate dicts."""
+    iq = _iq_arg(iq)
+    return psk31_sync_batch(iq.reshape(1, -1), fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand)[0]
+
+
+def best_psk31_sync(candidates, carrier_hz, baud=PSK31_BAUD):
+    """best_psk31_sync (__init__.pyi:615-625): of the candidates within 2 * baud of
+    carrier_hz the one with the highest score (the first of equals), or None."""
+    best = None
+    for c in candidates:
+        if abs(c["carrier_hz"] - carrier_hz) <= 2.0 * baud and (best is None or c["score"] > best["score"]):
+            best = c
+    return best
+
+
+def _varicode_text(bits) -> str:
+    d = VaricodeDecoder()
+    d.push_bits(np.ascontiguousarray(bits, np.uint8))
+    d.push_bits(np.zeros(2, np.uint8))
+    return "".join(chr(b) for b in d.pop_bytes() if 0x20 <= b < 0x7F)
+
+
+def psk31_decode_batch(iq, fs, base_hz, max_hz, min_carrier_syms=8, peak_margin_db=6.0, n_bits=1024, max_cand=10):
+    """The band browser: psk31_sync_batch, then each candidate's hard bits (soft >= 0) through
+    Varicode (printable ASCII kept, as Psk31Stream does). -> per channel a list of dicts
+    carrier_hz, score, time_sym, text."""
+    out = []
+    for cands in psk31_sync_batch(iq, fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand):
+        out.append([{"carrier_hz": c["carrier_hz"], "score": c["score"], "time_sym": c["time_sym"],
+                     "text": _varicode_text(c["soft_bits"] >= 0)} for c in cands])
+    return out
+
+
+def psk31_decode(iq, fs, base_hz, max_hz, min_carrier_syms=8, peak_margin_db=6.0, n_bits=1024, max_cand=10):
+    iq = _iq_arg(iq)
+    return psk31_decode_batch(iq.reshape(1, -1), fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand)[0]
+
+
+class Psk31Stream:
+    """Psk31Stream (codec/psk31.rs:416-572; __init__.pyi:567-585): feed(iq) -> newly decoded
+    printable text, flush() -> the rest. The demodulator runs on the device (a bank of one
+    stream; device=False: the library's scalar host demodulator), the decider or the
+    streaming Viterbi decoder and Varicode on the host. QPSK31 symbols with d_re^2 + d_im^2 <
+    0.01 are skipped (:519)."""
+
+    def __init__(self, mode: str, fs: float, carrier_hz: float, gain: float = 1.0, device: bool = True):
+        if mode not in ("bpsk", "qpsk"):
+            raise ValueError("mode: 'bpsk' or 'qpsk'")
+        self._qpsk = mode == "qpsk"
+        self._demod = (Qpsk31Demod if self._qpsk else Bpsk31Demod)(fs, carrier_hz, gain)
+        self._device = bool(device)
+        self._vit = StreamingViterbi() if self._qpsk else None
+        self._vdec = VaricodeDecoder()
+        self.fed_up_to = 0
+
+    def set_fed_up_to(self, v: int) -> None:
+        self.fed_up_to = int(v)
+
+    def _text(self, bits) -> str:
+        self._vdec.push_bits(np.ascontiguousarray(bits, np.uint8))
+        return "".join(chr(b) for b in self._vdec.pop_bytes() if 0x20 <= b < 0x7F)
+
+    def feed(self, iq) -> str:
+        iq = _iq_arg(iq)
+        if iq.size == 0:
+            return ""
+        soft = self._demod.process(iq) if self._device else self._demod.process_host(iq)[0]
+        self._demod._soft = []  # the stream decodes as it goes; nothing is kept for flush()
+        if not self._qpsk:
+            return self._text(soft >= 0)
+        pairs = soft.reshape(-1, 2)
+        re, im = pairs[:, 0], pairs[:, 1]
+        keep = ~(re * re + im * im < np.float32(0.01))
+        return self._text(self._vit.feed(np.ascontiguousarray(pairs[keep].reshape(-1))))
+
+    def flush(self) -> str:
+        text = self._text(self._vit.flush()) if self._qpsk else ""
+        return text + self._text(np.zeros(2, np.uint8))
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
