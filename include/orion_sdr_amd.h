@@ -797,6 +797,154 @@ int orion_psk31_demod_bank_reset(orion_psk31_demod_bank* b);
  * from; takes effect with the next call (which waits for the device once). */
 int orion_psk31_demod_bank_set_gain(orion_psk31_demod_bank* b, size_t index, float gain);
 
+/* ---- the OFDM symbol layer (src/multicarrier, modulate/ofdm.rs, demodulate/ofdm.rs) ----
+ * Two stated divergences from the reference: the transform takes powers of two from 8 to
+ * 4096 only (rustfft takes any length; ORION_E_ARG / NULL otherwise), and its rounding is
+ * this library's radix-2 transform's, not rustfft's. The handles keep the
+ * Block contract's shape (host pointers, orion_work_report) through their own process
+ * entries: the bit and LLR streams are not orion_block sample types. */
+#define ORION_OFDM_BPSK 0
+#define ORION_OFDM_QPSK 1
+#define ORION_OFDM_QAM16 2
+#define ORION_OFDM_QAM64 3
+#define ORION_OFDM_QAM256 4
+/* CarrierPlanError (multicarrier/config.rs:17-26) as orion_ofdm_config_validate returns it. */
+#define ORION_OFDM_PLAN_OK 0
+#define ORION_OFDM_PLAN_OUT_OF_RANGE 1
+#define ORION_OFDM_PLAN_OVERLAP 2
+#define ORION_OFDM_PLAN_EMPTY_DATA 3
+#define ORION_OFDM_PLAN_IN_GUARD_BAND 4
+/* EqualizerMethod (demodulate/ofdm.rs:297-321); NONE: no equalizer stage. */
+#define ORION_OFDM_EQ_NONE (-1)
+#define ORION_OFDM_EQ_TRAINING_SYMBOL_HOLD 0
+#define ORION_OFDM_EQ_PER_SYMBOL_PILOT_INTERP 1
+
+/* OfdmConfig::new over CarrierPlan::new(..).with_data_carriers(..).with_pilot_carriers(..)
+ * (modulate/ofdm.rs:139-166, multicarrier/config.rs:51-69): signed carrier indices, pilot_val
+ * [n_pilots] cf32. Nothing is validated here (orion_ofdm_config_validate does; the block
+ * constructors refuse an invalid configuration). */
+typedef struct orion_ofdm_config orion_ofdm_config;
+orion_ofdm_config* orion_ofdm_config_new(size_t n_fft, size_t cp_len, const int32_t* data_carriers, size_t n_data,
+                                         const int32_t* pilot_idx, const float* pilot_val, size_t n_pilots, float fs,
+                                         float rf_hz, float gain, int constellation);
+void orion_ofdm_config_free(orion_ofdm_config* c);
+/* with_contiguous_data (config.rs:128-149): appends to the data carriers. */
+int orion_ofdm_config_contiguous_data(orion_ofdm_config* c, size_t edge_guard, int include_dc);
+/* with_rx_window_backoff / with_symbol_window (modulate/ofdm.rs:240-259). */
+int orion_ofdm_config_set_rx_window_backoff(orion_ofdm_config* c, size_t backoff);
+int orion_ofdm_config_set_symbol_window(orion_ofdm_config* c, size_t roll_off);
+/* validate (config.rs:223-252), or validate_edge_guard (:262-278) when edge_guard >= 0:
+ * returns ORION_OFDM_PLAN_* (>= 0); bad_index (may be NULL) receives the offending carrier. */
+int orion_ofdm_config_validate(const orion_ofdm_config* c, long long edge_guard, int32_t* bad_index);
+/* info [8]: n_fft, cp_len, data carriers, pilots, bits_per_ofdm_symbol, samples_per_ofdm_symbol
+ * (modulate/ofdm.rs:359-365), occupied_half_carriers (config.rs:167-174), the window roll-off. */
+int orion_ofdm_config_info(const orion_ofdm_config* c, size_t* info);
+/* The data carriers (cap >= their count) and occupied_bins (config.rs:188-203; cap >= n_fft). */
+int orion_ofdm_config_data_carriers(const orion_ofdm_config* c, int32_t* out, size_t cap);
+int orion_ofdm_config_occupied_bins(const orion_ofdm_config* c, uint32_t* out, size_t cap, size_t* n);
+/* CarrierGrid::from_plan (grid.rs:40-66): data_bins [data carriers], pilot_bins [pilots]. */
+int orion_ofdm_config_grid(const orion_ofdm_config* c, uint32_t* data_bins, uint32_t* pilot_bins);
+/* SymbolFft::max_pilot_safe_backoff (symbol_fft.rs:90-92). */
+size_t orion_ofdm_max_pilot_safe_backoff(size_t n_fft, size_t pilot_spacing);
+
+/* Host only. The tables as the library holds them: axis [16] (build_axis_table,
+ * modulate/qam.rs:45-57) and thresholds [15] (build_threshold_table, demodulate/qam.rs:28-41)
+ * of a QAM order (zeros for BPSK / QPSK), the training pattern [n_fft] cf32
+ * (training_symbol_freq_pattern, sync/ofdm_sync.rs:270-272, :335-352), the transform's
+ * twiddles [n_fft / 2] cf32 and the window ramp [min(roll_off, symbol_len / 2)]
+ * (symbol_window.rs:47-59). Any output may be NULL. */
+int orion_ofdm_tables(int constellation, float* axis, float* thresholds, size_t n_fft, float* training,
+                      float* twiddles, size_t symbol_len, size_t roll_off, float* ramp);
+/* Host only: the mappers, hard deciders and max-log LLRs on n_syms symbols
+ * (modulate/qpsk.rs:33-45, qam.rs:92-101; demodulate/qam.rs:120-140, ofdm.rs:588-638). */
+int orion_ofdm_map_host(int constellation, const uint8_t* bits, size_t n_syms, void* syms);
+int orion_ofdm_decide_host(int constellation, const void* syms, size_t n_syms, uint8_t* bits);
+int orion_ofdm_llr_host(int constellation, const void* syms, size_t n_syms, float* llr);
+/* Host only: the scalar radix-2 transform of n_sym n_fft-point symbols, in place allowed. */
+int orion_fft_host(size_t n_fft, int inverse, const void* in, size_t n_sym, void* out);
+/* Host only: SymbolWindow (symbol_window.rs:80-98) over n_sym symbols in place. */
+int orion_ofdm_window_host(size_t symbol_len, size_t roll_off, void* iq, size_t n_sym);
+/* Host only: Rotator::next n times from a fresh oscillator (dsp/rotator.rs:16-61). */
+int orion_ofdm_rotator_host(float freq_hz, float fs, size_t n, void* out);
+/* Host only: evm_db (demodulate/ofdm.rs:263-293); *valid 0 where the reference gives None. */
+int orion_ofdm_evm_db_host(int constellation, const void* soft, size_t n_soft, const uint8_t* bits, size_t n_bits,
+                           size_t num_symbols, float* evm_db, int* valid);
+/* Host only: equalizer_weight (demodulate/ofdm.rs:495-502) of n channel estimates, and
+ * interpolate_at (:514-537) over n_pilots bin-sorted ratios at n_bins bins. */
+int orion_ofdm_equalizer_weight_host(const void* h, size_t n, void* w);
+int orion_ofdm_interpolate_host(const uint32_t* pilot_bins, const void* ratios, size_t n_pilots, const uint32_t* bins,
+                                size_t n_bins, void* out);
+
+/* FftBlock / IfftBlock (multicarrier/fft.rs:16-120). NULL (and a message) for a size that is
+ * not a power of two from 8 to 4096. No device is touched here. */
+typedef struct orion_fft orion_fft;
+orion_fft* orion_fft_new(size_t n_fft);
+orion_fft* orion_ifft_new(size_t n_fft);
+void orion_fft_free(orion_fft* f);
+/* One symbol per call, host pointers; a short input or output gives a zero report (fft.rs:42-46). */
+int orion_fft_process(orion_fft* f, const void* in, size_t n_in, void* out, size_t out_cap, orion_work_report* report);
+/* batch symbols over resident buffers: symbol b reads in + b * in_stride and writes out + b *
+ * out_stride (strides in cf32 values, >= n_fft; any 8-byte aligned address). */
+int orion_fft_batch(orion_fft* f, const void* in, size_t in_stride, void* out, size_t out_stride, size_t batch,
+                    void* stream);
+
+/* OfdmMod, OfdmDemod (+ an optional OfdmEqualizer stage), OfdmDecider, OfdmSoftDemod and
+ * OfdmEqualizer (modulate/ofdm.rs:422-544, demodulate/ofdm.rs:26-166, :333-569, :693-731) of
+ * one configuration, which is copied. NULL (and a message) for a configuration that does not
+ * validate, a transform size outside 8..4096, cp_len > n_fft or an unknown constellation.
+ * No device is touched here. */
+typedef struct orion_ofdm orion_ofdm;
+orion_ofdm* orion_ofdm_mod_new(const orion_ofdm_config* c);
+orion_ofdm* orion_ofdm_demod_new(const orion_ofdm_config* c, int equalizer);
+orion_ofdm* orion_ofdm_decider_new(const orion_ofdm_config* c);
+orion_ofdm* orion_ofdm_soft_demod_new(const orion_ofdm_config* c);
+orion_ofdm* orion_ofdm_equalizer_new(const orion_ofdm_config* c, int method);
+void orion_ofdm_free(orion_ofdm* h);
+/* set_gain of the modulator or demodulator (modulate/ofdm.rs:463-465, demodulate/ofdm.rs:50-52);
+ * reset: the RF rotator back to phase 0. */
+int orion_ofdm_set_gain(orion_ofdm* h, float gain);
+int orion_ofdm_reset(orion_ofdm* h);
+/* estimate_from_training_symbol (demodulate/ofdm.rs:440-448) of a demodulator's or an
+ * equalizer's TrainingSymbolHold stage: received [n_fft] cf32, host memory. */
+int orion_ofdm_estimate_channel(orion_ofdm* h, const void* received_freq, size_t n);
+/* The Block contract, host pointers, on the device: as many whole symbols as fit in both
+ * buffers (the reference's process takes one; k calls of it equal one call here); a short
+ * input or output gives a zero report. Modulator: bits u8 -> cf32; demodulator: cf32 ->
+ * cf32 soft symbols; decider: cf32 -> bits u8; soft demodulator: cf32 -> f32 LLRs;
+ * equalizer: cf32 n_fft-bin vectors -> the same. Sizes count elements. */
+int orion_ofdm_process(orion_ofdm* h, const void* in, size_t n_in, void* out, size_t out_cap,
+                       orion_work_report* report);
+/* Resident buffers, n_channels x n_symbols symbols in one launch, asynchronous on stream.
+ * Modulator: bits [n_channels][n_symbols * bits_per_ofdm_symbol] -> iq [n_channels][n_symbols
+ * * samples_per_ofdm_symbol]; with rf_hz != 0 every channel continues the handle's rotator
+ * from the same phase, which then advances by one channel's samples. */
+int orion_ofdm_mod_device(orion_ofdm* h, const uint8_t* bits, size_t n_channels, size_t n_symbols, void* iq,
+                          void* stream);
+/* Demodulator: iq -> soft [n_channels][n_symbols * data carriers] cf32 and, from the same
+ * launch where not NULL, bits (u8) and llr (f32) [n_channels][n_symbols * bits_per_ofdm_symbol]. */
+int orion_ofdm_demod_device(orion_ofdm* h, const void* iq, size_t n_channels, size_t n_symbols, void* soft,
+                            uint8_t* bits, float* llr, void* stream);
+/* Decider / soft demodulator over n_channels * n_symbols * data carriers soft symbols;
+ * equalizer over n_channels * n_symbols n_fft-bin vectors. */
+int orion_ofdm_decider_device(orion_ofdm* h, const void* soft, size_t n_channels, size_t n_symbols, uint8_t* bits,
+                              void* stream);
+int orion_ofdm_soft_demod_device(orion_ofdm* h, const void* soft, size_t n_channels, size_t n_symbols, float* llr,
+                                 void* stream);
+int orion_ofdm_equalizer_device(orion_ofdm* h, const void* in, size_t n_channels, size_t n_symbols, void* out,
+                                void* stream);
+/* Host only, the scalar restatement the kernels are held to: OfdmMod::process over whole
+ * symbols from the handle's state, OfdmDemod::process (through the handle's equalizer
+ * stage, when it has one), OfdmEqualizer::process. Reports as orion_ofdm_process. */
+int orion_ofdm_mod_host(orion_ofdm* h, const uint8_t* bits, size_t n_bits, void* iq, size_t out_cap,
+                        orion_work_report* report);
+int orion_ofdm_demod_host(orion_ofdm* h, const void* iq, size_t n, void* soft, size_t out_cap,
+                          orion_work_report* report);
+int orion_ofdm_equalize_host(orion_ofdm* h, const void* in, size_t n, void* out, size_t out_cap,
+                             orion_work_report* report);
+/* Host only: set_pilot_bins (demodulate/ofdm.rs:426-432) of an equalizer's host stage. */
+int orion_ofdm_set_pilot_bins_host(orion_ofdm* h, const uint32_t* pilot_bins, const void* pilot_val, size_t n_pilots,
+                                   const uint32_t* data_bins, size_t n_data);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@
 
 #include "blocks.hpp"
 #include "ldpc.hpp"
+#include "ofdm.hpp"
+#include "ofdm_blocks.hpp"
 #include "osc.hpp"
 #include "psk31.hpp"
 #include "psk31_blocks.hpp"
@@ -50,6 +52,24 @@ struct orion_psk31_demod_bank {
   orion_psk31_demod_bank(float fs, const orion::psk31::Stream* streams, size_t nstreams, size_t nch)
       : impl(fs, streams, nstreams, nch) {}
 };
+struct orion_ofdm_config {
+  orion::ofdm::Config impl;
+};
+struct orion_fft {
+  orion::FftDev impl;
+  orion_fft(size_t n, bool inverse) : impl(n, inverse) {}
+};
+enum { kOfdmMod = 0, kOfdmDemod = 1, kOfdmDecider = 2, kOfdmSoftDemod = 3, kOfdmEqualizer = 4 };
+struct orion_ofdm {
+  int kind;
+  orion::OfdmEngine impl;
+  orion_ofdm(int k, const orion::ofdm::Config& c, int eq) : kind(k), impl(c, eq) {}
+};
+static_assert(ORION_OFDM_BPSK == orion::ofdm::kBpsk && ORION_OFDM_QAM256 == orion::ofdm::kQam256 &&
+                  ORION_OFDM_PLAN_IN_GUARD_BAND == orion::ofdm::kPlanInGuardBand &&
+                  ORION_OFDM_EQ_NONE == orion::ofdm::kEqNone &&
+                  ORION_OFDM_EQ_PER_SYMBOL_PILOT_INTERP == orion::ofdm::kEqPerSymbolPilotInterp,
+              "the header's OFDM constants are ofdm.hpp's");
 static_assert(sizeof(orion_psk31_signal) == sizeof(orion::psk31::Signal) && sizeof(orion_psk31_signal) == 32,
               "orion_psk31_signal is psk31.hpp's record");
 static_assert(sizeof(orion_psk31_stream) == sizeof(orion::psk31::Stream) && sizeof(orion_psk31_stream) == 32 &&
@@ -1367,6 +1387,417 @@ int orion_psk31_demod_bank_reset(orion_psk31_demod_bank* b) {
   if (!b) return fail(ORION_E_NULL, "null handle");
   return guarded([&] {
     b->impl.reset();
+    return ORION_OK;
+  });
+}
+
+// ---- the OFDM symbol layer --------------------------------------------------------------
+orion_ofdm_config* orion_ofdm_config_new(size_t n_fft, size_t cp_len, const int32_t* data_carriers, size_t n_data,
+                                         const int32_t* pilot_idx, const float* pilot_val, size_t n_pilots, float fs,
+                                         float rf_hz, float gain, int constellation) {
+  if ((n_data && !data_carriers) || (n_pilots && (!pilot_idx || !pilot_val))) {
+    fail(ORION_E_NULL, "null buffer");
+    return nullptr;
+  }
+  try {
+    auto c = new orion_ofdm_config;
+    c->impl.plan.n_fft = n_fft;
+    c->impl.plan.cp_len = cp_len;
+    c->impl.plan.data.assign(data_carriers, data_carriers + n_data);
+    c->impl.plan.pilot_idx.assign(pilot_idx, pilot_idx + n_pilots);
+    c->impl.plan.pilot_val.assign(pilot_val, pilot_val + 2 * n_pilots);
+    c->impl.fs = fs;
+    c->impl.rf_hz = rf_hz;
+    c->impl.gain = gain;
+    c->impl.constellation = constellation;
+    return c;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_ofdm_config_free(orion_ofdm_config* c) { delete c; }
+int orion_ofdm_config_contiguous_data(orion_ofdm_config* c, size_t edge_guard, int include_dc) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  if (c->impl.plan.n_fft > (size_t{1} << 24)) return fail(ORION_E_ARG, "n_fft above 2^24");
+  return guarded([&] {
+    orion::ofdm::plan_contiguous_data(c->impl.plan, edge_guard, include_dc != 0);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_config_set_rx_window_backoff(orion_ofdm_config* c, size_t backoff) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  c->impl.rx_window_backoff = backoff;
+  return ORION_OK;
+}
+int orion_ofdm_config_set_symbol_window(orion_ofdm_config* c, size_t roll_off) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  c->impl.plan.roll_off = roll_off;
+  return ORION_OK;
+}
+int orion_ofdm_config_validate(const orion_ofdm_config* c, long long edge_guard, int32_t* bad_index) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    return edge_guard >= 0
+               ? orion::ofdm::plan_validate_edge_guard(c->impl.plan, static_cast<size_t>(edge_guard), bad_index)
+               : orion::ofdm::plan_validate(c->impl.plan, bad_index);
+  });
+}
+int orion_ofdm_config_info(const orion_ofdm_config* c, size_t* info) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  if (!info) return fail(ORION_E_NULL, "null buffer");
+  const orion::ofdm::Config& k = c->impl;
+  info[0] = k.plan.n_fft;
+  info[1] = k.plan.cp_len;
+  info[2] = k.plan.data.size();
+  info[3] = k.plan.pilot_idx.size();
+  info[4] = k.bits_per_ofdm_symbol();
+  info[5] = k.samples_per_ofdm_symbol();
+  info[6] = orion::ofdm::plan_occupied_half_carriers(k.plan);
+  info[7] = k.plan.roll_off;
+  return ORION_OK;
+}
+int orion_ofdm_config_data_carriers(const orion_ofdm_config* c, int32_t* out, size_t cap) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  const auto& d = c->impl.plan.data;
+  if (cap < d.size()) return fail(ORION_E_ARG, "cap below the data-carrier count");
+  if (!d.empty() && !out) return fail(ORION_E_NULL, "null buffer");
+  std::copy(d.begin(), d.end(), out);
+  return ORION_OK;
+}
+int orion_ofdm_config_occupied_bins(const orion_ofdm_config* c, uint32_t* out, size_t cap, size_t* n) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  if (!n) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<size_t> b = orion::ofdm::plan_occupied_bins(c->impl.plan);
+    if (cap < b.size()) return fail(ORION_E_ARG, "cap below the occupied-bin count");
+    if (!b.empty() && !out) return fail(ORION_E_NULL, "null buffer");
+    for (size_t i = 0; i < b.size(); ++i) out[i] = static_cast<uint32_t>(b[i]);
+    *n = b.size();
+    return ORION_OK;
+  });
+}
+int orion_ofdm_config_grid(const orion_ofdm_config* c, uint32_t* data_bins, uint32_t* pilot_bins) {
+  if (!c) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    const orion::ofdm::Grid g = orion::ofdm::grid_from_plan(c->impl.plan);
+    if ((!g.data_bins.empty() && !data_bins) || (!g.pilot_bins.empty() && !pilot_bins))
+      return fail(ORION_E_NULL, "null buffer");
+    std::copy(g.data_bins.begin(), g.data_bins.end(), data_bins);
+    std::copy(g.pilot_bins.begin(), g.pilot_bins.end(), pilot_bins);
+    return ORION_OK;
+  });
+}
+size_t orion_ofdm_max_pilot_safe_backoff(size_t n_fft, size_t pilot_spacing) {
+  return orion::ofdm::max_pilot_safe_backoff(n_fft, pilot_spacing);
+}
+int orion_ofdm_tables(int constellation, float* axis, float* thresholds, size_t n_fft, float* training, float* twiddles,
+                      size_t symbol_len, size_t roll_off, float* ramp) {
+  return guarded([&] {
+    const size_t bps = orion::ofdm::bits_per_symbol(constellation);
+    if ((axis || thresholds) && bps == 0) return fail(ORION_E_ARG, "unknown constellation");
+    if (axis) {
+      std::fill(axis, axis + 16, 0.0f);
+      if (bps >= 4) orion::ofdm::axis_table(bps, axis);
+    }
+    if (thresholds) {
+      std::fill(thresholds, thresholds + 15, 0.0f);
+      if (bps >= 4) orion::ofdm::threshold_table(bps, thresholds);
+    }
+    if ((training || twiddles) && n_fft > (size_t{1} << 24)) return fail(ORION_E_ARG, "n_fft above 2^24");
+    if (training) orion::ofdm::training_pattern(n_fft, training);
+    if (twiddles) {
+      const std::vector<float> tw = orion::ofdm::fft_twiddles(n_fft);
+      std::copy(tw.begin(), tw.end(), twiddles);
+    }
+    if (ramp) {
+      if (roll_off > (size_t{1} << 30)) return fail(ORION_E_ARG, "roll_off above 2^30");
+      const std::vector<float> r = orion::ofdm::window_ramp(symbol_len, roll_off);
+      std::copy(r.begin(), r.end(), ramp);
+    }
+    return ORION_OK;
+  });
+}
+int orion_ofdm_map_host(int constellation, const uint8_t* bits, size_t n_syms, void* syms) {
+  if (n_syms && (!bits || !syms)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    if (orion::ofdm::bits_per_symbol(constellation) == 0) return fail(ORION_E_ARG, "unknown constellation");
+    orion::ofdm::map_bits(constellation, bits, n_syms, static_cast<float*>(syms));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_decide_host(int constellation, const void* syms, size_t n_syms, uint8_t* bits) {
+  if (n_syms && (!bits || !syms)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    if (orion::ofdm::bits_per_symbol(constellation) == 0) return fail(ORION_E_ARG, "unknown constellation");
+    orion::ofdm::decide(constellation, static_cast<const float*>(syms), n_syms, bits);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_llr_host(int constellation, const void* syms, size_t n_syms, float* llr) {
+  if (n_syms && (!llr || !syms)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    if (orion::ofdm::bits_per_symbol(constellation) == 0) return fail(ORION_E_ARG, "unknown constellation");
+    orion::ofdm::soft_llr(constellation, static_cast<const float*>(syms), n_syms, llr);
+    return ORION_OK;
+  });
+}
+int orion_fft_host(size_t n_fft, int inverse, const void* in, size_t n_sym, void* out) {
+  if (n_sym && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::ofdm::Fft f(n_fft, inverse != 0);
+    size_t r, w;
+    for (size_t s = 0; s < n_sym; ++s)
+      f.process(static_cast<const float*>(in) + 2 * s * n_fft, n_fft, static_cast<float*>(out) + 2 * s * n_fft, n_fft,
+                &r, &w);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_window_host(size_t symbol_len, size_t roll_off, void* iq, size_t n_sym) {
+  if (n_sym && symbol_len && !iq) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<float> r = orion::ofdm::window_ramp(symbol_len, std::min<size_t>(roll_off, symbol_len));
+    for (size_t s = 0; s < n_sym; ++s) orion::ofdm::window_apply(static_cast<float*>(iq) + 2 * s * symbol_len, symbol_len, r);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_rotator_host(float freq_hz, float fs, size_t n, void* out) {
+  if (n && !out) return fail(ORION_E_NULL, "null buffer");
+  orion::ofdm::Rotator r(freq_hz, fs);
+  float* o = static_cast<float*>(out);
+  for (size_t i = 0; i < n; ++i) r.next(o + 2 * i, o + 2 * i + 1);
+  return ORION_OK;
+}
+int orion_ofdm_evm_db_host(int constellation, const void* soft, size_t n_soft, const uint8_t* bits, size_t n_bits,
+                           size_t num_symbols, float* evm_db, int* valid) {
+  if (!evm_db || !valid || (n_soft && !soft) || (n_bits && !bits)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    *valid = orion::ofdm::evm_db(constellation, static_cast<const float*>(soft), n_soft, bits, n_bits, num_symbols, evm_db)
+                 ? 1
+                 : 0;
+    return ORION_OK;
+  });
+}
+int orion_ofdm_equalizer_weight_host(const void* h, size_t n, void* w) {
+  if (n && (!h || !w)) return fail(ORION_E_NULL, "null buffer");
+  const float* hp = static_cast<const float*>(h);
+  float* wp = static_cast<float*>(w);
+  for (size_t i = 0; i < n; ++i) orion::ofdm::equalizer_weight(hp[2 * i], hp[2 * i + 1], wp + 2 * i, wp + 2 * i + 1);
+  return ORION_OK;
+}
+int orion_ofdm_interpolate_host(const uint32_t* pilot_bins, const void* ratios, size_t n_pilots, const uint32_t* bins,
+                                size_t n_bins, void* out) {
+  if (n_pilots == 0) return fail(ORION_E_ARG, "interpolate_at needs at least one pilot");
+  if (!pilot_bins || !ratios || (n_bins && (!bins || !out))) return fail(ORION_E_NULL, "null buffer");
+  for (size_t i = 0; i + 1 < n_pilots; ++i)
+    if (pilot_bins[i] >= pilot_bins[i + 1]) return fail(ORION_E_ARG, "pilot bins not strictly ascending");
+  float* o = static_cast<float*>(out);
+  for (size_t i = 0; i < n_bins; ++i)
+    orion::ofdm::interpolate_at(pilot_bins, static_cast<const float*>(ratios), n_pilots, bins[i], o + 2 * i, o + 2 * i + 1);
+  return ORION_OK;
+}
+
+static orion_fft* fft_new(size_t n_fft, bool inverse) {
+  try {
+    return new orion_fft(n_fft, inverse);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+orion_fft* orion_fft_new(size_t n_fft) { return fft_new(n_fft, false); }
+orion_fft* orion_ifft_new(size_t n_fft) { return fft_new(n_fft, true); }
+void orion_fft_free(orion_fft* f) { delete f; }
+int orion_fft_process(orion_fft* f, const void* in, size_t n_in, void* out, size_t out_cap, orion_work_report* report) {
+  if (!f) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n_in && !in) || (out_cap && !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::WorkReport w = f->impl.process_host(in, n_in, out, out_cap);
+    report->in_read = w.in_read;
+    report->out_written = w.out_written;
+    return ORION_OK;
+  });
+}
+int orion_fft_batch(orion_fft* f, const void* in, size_t in_stride, void* out, size_t out_stride, size_t batch,
+                    void* stream) {
+  if (!f) return fail(ORION_E_NULL, "null handle");
+  if (batch && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    f->impl.batch(in, in_stride, out, out_stride, batch, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+
+static orion_ofdm* ofdm_new(int kind, const orion_ofdm_config* c, int eq) {
+  if (!c) {
+    fail(ORION_E_NULL, "null configuration");
+    return nullptr;
+  }
+  try {
+    return new orion_ofdm(kind, c->impl, eq);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+orion_ofdm* orion_ofdm_mod_new(const orion_ofdm_config* c) { return ofdm_new(kOfdmMod, c, ORION_OFDM_EQ_NONE); }
+orion_ofdm* orion_ofdm_demod_new(const orion_ofdm_config* c, int equalizer) { return ofdm_new(kOfdmDemod, c, equalizer); }
+orion_ofdm* orion_ofdm_decider_new(const orion_ofdm_config* c) { return ofdm_new(kOfdmDecider, c, ORION_OFDM_EQ_NONE); }
+orion_ofdm* orion_ofdm_soft_demod_new(const orion_ofdm_config* c) {
+  return ofdm_new(kOfdmSoftDemod, c, ORION_OFDM_EQ_NONE);
+}
+orion_ofdm* orion_ofdm_equalizer_new(const orion_ofdm_config* c, int method) {
+  if (method == ORION_OFDM_EQ_NONE) {
+    fail(ORION_E_ARG, "an equalizer needs a method");
+    return nullptr;
+  }
+  return ofdm_new(kOfdmEqualizer, c, method);
+}
+void orion_ofdm_free(orion_ofdm* h) { delete h; }
+int orion_ofdm_set_gain(orion_ofdm* h, float gain) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind == kOfdmMod)
+    h->impl.set_mod_gain(gain);
+  else if (h->kind == kOfdmDemod)
+    h->impl.set_demod_gain(gain);
+  else
+    return fail(ORION_E_TYPE, "not a modulator or demodulator");
+  return ORION_OK;
+}
+int orion_ofdm_reset(orion_ofdm* h) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  return guarded([&] {
+    h->impl.reset();
+    return ORION_OK;
+  });
+}
+int orion_ofdm_estimate_channel(orion_ofdm* h, const void* received_freq, size_t n) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (n && !received_freq) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.estimate_channel(static_cast<const float*>(received_freq), n);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_process(orion_ofdm* h, const void* in, size_t n_in, void* out, size_t out_cap,
+                       orion_work_report* report) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n_in && !in) || (out_cap && !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::WorkReport w;
+    switch (h->kind) {
+      case kOfdmMod: w = h->impl.mod_host(static_cast<const uint8_t*>(in), n_in, out, out_cap); break;
+      case kOfdmDemod: w = h->impl.demod_host(in, n_in, out, out_cap); break;
+      case kOfdmDecider: w = h->impl.decide_host(in, n_in, static_cast<uint8_t*>(out), out_cap); break;
+      case kOfdmSoftDemod: w = h->impl.soft_demod_host(in, n_in, static_cast<float*>(out), out_cap); break;
+      default: w = h->impl.equalize_host(in, n_in, out, out_cap); break;
+    }
+    report->in_read = w.in_read;
+    report->out_written = w.out_written;
+    return ORION_OK;
+  });
+}
+int orion_ofdm_mod_device(orion_ofdm* h, const uint8_t* bits, size_t n_channels, size_t n_symbols, void* iq,
+                          void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmMod) return fail(ORION_E_TYPE, "not a modulator");
+  if (n_channels && n_symbols && (!bits || !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.modulate(bits, n_channels, n_symbols, iq, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_demod_device(orion_ofdm* h, const void* iq, size_t n_channels, size_t n_symbols, void* soft,
+                            uint8_t* bits, float* llr, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmDemod) return fail(ORION_E_TYPE, "not a demodulator");
+  if (n_channels && n_symbols && (!iq || !soft)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.demodulate(iq, n_channels, n_symbols, soft, bits, llr, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+static int ofdm_count(size_t a, size_t b, size_t c, size_t* out) {
+  if (a > (size_t{1} << 30) || b > (size_t{1} << 30) || a * b > (size_t{1} << 30) || c > (size_t{1} << 24)) return -1;
+  *out = a * b * c;
+  return 0;
+}
+int orion_ofdm_decider_device(orion_ofdm* h, const void* soft, size_t n_channels, size_t n_symbols, uint8_t* bits,
+                              void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmDecider) return fail(ORION_E_TYPE, "not a decider");
+  if (n_channels && n_symbols && (!soft || !bits)) return fail(ORION_E_NULL, "null buffer");
+  size_t n;
+  if (ofdm_count(n_channels, n_symbols, h->impl.num_data(), &n)) return fail(ORION_E_ARG, "more than 2^30 symbols");
+  return guarded([&] {
+    h->impl.decide(soft, n, bits, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_soft_demod_device(orion_ofdm* h, const void* soft, size_t n_channels, size_t n_symbols, float* llr,
+                                 void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmSoftDemod) return fail(ORION_E_TYPE, "not a soft demodulator");
+  if (n_channels && n_symbols && (!soft || !llr)) return fail(ORION_E_NULL, "null buffer");
+  size_t n;
+  if (ofdm_count(n_channels, n_symbols, h->impl.num_data(), &n)) return fail(ORION_E_ARG, "more than 2^30 symbols");
+  return guarded([&] {
+    h->impl.soft_demod(soft, n, llr, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_equalizer_device(orion_ofdm* h, const void* in, size_t n_channels, size_t n_symbols, void* out,
+                                void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmEqualizer) return fail(ORION_E_TYPE, "not an equalizer");
+  if (n_channels && n_symbols && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  size_t n;
+  if (ofdm_count(n_channels, n_symbols, 1, &n)) return fail(ORION_E_ARG, "more than 2^30 symbols");
+  return guarded([&] {
+    h->impl.equalize(in, n, out, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_mod_host(orion_ofdm* h, const uint8_t* bits, size_t n_bits, void* iq, size_t out_cap,
+                        orion_work_report* report) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n_bits && !bits) || (out_cap && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.mod().process(bits, n_bits, static_cast<float*>(iq), out_cap, &report->in_read, &report->out_written);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_demod_host(orion_ofdm* h, const void* iq, size_t n, void* soft, size_t out_cap,
+                          orion_work_report* report) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!report || (n && !iq) || (out_cap && !soft)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.demod().process(static_cast<const float*>(iq), n, static_cast<float*>(soft), out_cap, h->impl.equalizer(),
+                            &report->in_read, &report->out_written);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_equalize_host(orion_ofdm* h, const void* in, size_t n, void* out, size_t out_cap,
+                             orion_work_report* report) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (!h->impl.equalizer()) return fail(ORION_E_TYPE, "this handle has no equalizer");
+  if (!report || (n && !in) || (out_cap && !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const size_t nf = h->impl.equalizer()->n_fft(), k = std::min(n / nf, out_cap / nf);
+    size_t r, w;
+    for (size_t s = 0; s < k; ++s)
+      h->impl.equalizer()->process(static_cast<const float*>(in) + 2 * s * nf, nf, static_cast<float*>(out) + 2 * s * nf,
+                                   nf, &r, &w);
+    report->in_read = report->out_written = k * nf;
+    return ORION_OK;
+  });
+}
+int orion_ofdm_set_pilot_bins_host(orion_ofdm* h, const uint32_t* pilot_bins, const void* pilot_val, size_t n_pilots,
+                                   const uint32_t* data_bins, size_t n_data) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if ((n_pilots && (!pilot_bins || !pilot_val)) || (n_data && !data_bins)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.set_pilot_bins(pilot_bins, static_cast<const float*>(pilot_val), n_pilots, data_bins, n_data);
     return ORION_OK;
   });
 }

@@ -1,0 +1,391 @@
+// k_ofdm.hip — the OFDM symbol layer on the device: the batched transform (k_fft), the fused
+// modulator (k_ofdm_mod: mapper, grid scatter, inverse transform, cyclic prefix, window,
+// gain) and demodulator (k_ofdm_demod: window select, forward transform, equalizer, grid
+// gather, gain, hard bits / LLRs), the RF stage (k_ofdm_rf) and the elementwise blocks a
+// caller composes by hand (k_ofdm_decide, k_ofdm_llr, k_ofdm_equalize).
+//
+// The transform. One symbol lives in LDS; kOfdmThreads / T symbols share a workgroup, T =
+// min(n / 4, kOfdmThreads) lanes each, so that a workgroup's four waves are full at every
+// size. fft_lds is radix-2 decimation in time, two stages fused per pass: a lane holds the
+// four values of a radix-4 butterfly in registers, so a pass costs one LDS read and one LDS
+// write per value where two radix-2 passes cost two; a first radix-2 pass when log2 n is
+// odd. The arithmetic of each fused stage is the host's (ofdm.cpp fft_inplace): the same
+// twiddle table, t = b w with four multiplies, one subtraction and one addition, each
+// rounded (-ffp-contract=off), W^0 multiplied like any other, then a + t and a - t. The
+// input is written to LDS in bit-reversed order (__brev) and the output read in natural
+// order. The stand-alone block and both fused kernels call this one function, so they give
+// identical bits for identical input, and those bits are the host transform's.
+// LDS index p is stored at p + (p >> 5): the bit-reversed placement of consecutive samples
+// strides by n / 64 values, which without the skew lands every lane of a group in one bank.
+//
+// Global accesses are 8-byte (one cf32 per lane, consecutive lanes consecutive values):
+// always aligned for cf32 data at any 8-byte offset, so an odd symbol stride needs no
+// fallback path.
+#include "hip_common.hpp"
+#include "ofdm_blocks.hpp"
+
+namespace orion {
+
+namespace {
+__device__ __forceinline__ int pad(int p) { return p + (p >> 5); }
+__device__ __forceinline__ int brev(int k, int log2n) { return static_cast<int>(__brev(static_cast<unsigned>(k)) >> (32 - log2n)); }
+// b w, the host's butterfly product.
+__device__ __forceinline__ f2 twmul(f2 d, f2 w) { return f2{d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x}; }
+__device__ __forceinline__ f2 twid(const f2* __restrict__ tw, int k, bool inv) {
+  f2 w = tw[k];
+  if (inv) w.y = -w.y;
+  return w;
+}
+
+// In place over x (one symbol, bit-reversed order in, natural order out). Every lane of the
+// workgroup calls it (the barriers are the workgroup's); t < T indexes the symbol's lanes.
+__device__ __forceinline__ void fft_lds(f2* x, int n, int log2n, const f2* __restrict__ tw, bool inv, int t, int T) {
+  int cur = 1;  // the size of the transforms already done
+  if (log2n & 1) {
+    __syncthreads();
+    const f2 w = twid(tw, 0, inv);
+    for (int q = t; q < (n >> 1); q += T) {
+      const f2 a = x[pad(2 * q)], tt = twmul(x[pad(2 * q + 1)], w);
+      x[pad(2 * q)] = a + tt;
+      x[pad(2 * q + 1)] = a - tt;
+    }
+    cur = 2;
+  }
+  while (cur < n) {  // the stages of size len = 2 cur and 2 len in one pass
+    __syncthreads();
+    const int len = 2 * cur, half = cur, step = n / len;
+    for (int q = t; q < (n >> 2); q += T) {
+      const int j = q & (half - 1);
+      const int base = ((q - j) << 2) + j;
+      const f2 x0 = x[pad(base)], x1 = x[pad(base + half)], x2 = x[pad(base + len)], x3 = x[pad(base + len + half)];
+      // the stage of size len: pairs (x0, x1) and (x2, x3), both at offset j
+      const f2 w1 = twid(tw, j * step, inv);
+      const f2 t1 = twmul(x1, w1), t3 = twmul(x3, w1);
+      const f2 y0 = x0 + t1, y1 = x0 - t1, y2 = x2 + t3, y3 = x2 - t3;
+      // the stage of size 2 len: pairs (y0, y2) at offset j and (y1, y3) at offset j + half
+      const f2 t2 = twmul(y2, twid(tw, j * (step >> 1), inv));
+      const f2 t4 = twmul(y3, twid(tw, (j + half) * (step >> 1), inv));
+      x[pad(base)] = y0 + t2;
+      x[pad(base + len)] = y0 - t2;
+      x[pad(base + half)] = y1 + t4;
+      x[pad(base + len + half)] = y1 - t4;
+    }
+    cur <<= 2;
+  }
+  __syncthreads();
+}
+
+// ---- constellations (ofdm.cpp map_bits / decide / soft_llr) ---------------------------
+__device__ __forceinline__ f2 map_point(int order, const uint8_t* __restrict__ b, const float* __restrict__ axis) {
+  const float r = 0.70710678118654752440f;
+  if (order == ofdm::kBpsk) return f2{(b[0] & 1u) == 0 ? 1.0f : -1.0f, 0.0f};
+  if (order == ofdm::kQpsk) return f2{(b[0] & 1u) == 0 ? r : -r, (b[1] & 1u) == 0 ? r : -r};
+  const int k = order;  // kQam16 = 2, kQam64 = 3, kQam256 = 4: the bits per axis
+  int ii = 0, iq = 0;
+  for (int i = 0; i < k; ++i) {
+    ii = (ii << 1) | (b[i] & 1);
+    iq = (iq << 1) | (b[k + i] & 1);
+  }
+  return f2{axis[ii], axis[iq]};
+}
+__device__ __forceinline__ int decide_axis(float v, int k, const float* __restrict__ thr) {
+  int nat = 0;
+  for (int t = 0; t < (1 << k) - 1; ++t) nat += v > thr[t] ? 1 : 0;
+  return nat ^ (nat >> 1);
+}
+__device__ __forceinline__ void decide_sym(int order, f2 v, const float* __restrict__ thr, uint8_t* __restrict__ out) {
+  if (order == ofdm::kBpsk) {
+    out[0] = v.x < 0.0f ? 1 : 0;
+  } else if (order == ofdm::kQpsk) {
+    out[0] = v.x < 0.0f ? 1 : 0;
+    out[1] = v.y < 0.0f ? 1 : 0;
+  } else {
+    const int k = order;
+    const int gi = decide_axis(v.x, k, thr), gq = decide_axis(v.y, k, thr);
+    for (int b = 0; b < k; ++b) {
+      out[b] = static_cast<uint8_t>((gi >> (k - 1 - b)) & 1);
+      out[k + b] = static_cast<uint8_t>((gq >> (k - 1 - b)) & 1);
+    }
+  }
+}
+__device__ __forceinline__ void axis_llr(float v, int k, const float* __restrict__ axis, float* __restrict__ out) {
+  for (int b = 0; b < k; ++b) {
+    const int shift = k - 1 - b;
+    float d0 = __builtin_inff(), d1 = __builtin_inff();
+    for (int g = 0; g < (1 << k); ++g) {
+      const float d = (v - axis[g]) * (v - axis[g]);
+      if (((g >> shift) & 1) == 0)
+        d0 = fminf(d0, d);
+      else
+        d1 = fminf(d1, d);
+    }
+    out[b] = d1 - d0;
+  }
+}
+__device__ __forceinline__ void llr_sym(int order, f2 v, const float* __restrict__ axis, float* __restrict__ out) {
+  if (order == ofdm::kBpsk) {
+    out[0] = 4.0f * v.x;
+  } else if (order == ofdm::kQpsk) {
+    const float scale = 4.0f * 1.41421356237309504880f;
+    out[0] = scale * v.x;
+    out[1] = scale * v.y;
+  } else {
+    const int k = order;
+    axis_llr(v.x, k, axis, out);
+    axis_llr(v.y, k, axis, out + k);
+  }
+}
+
+// ---- the equalizer (ofdm.cpp cdiv / equalizer_weight / interpolate_at) ----------------
+__device__ __forceinline__ f2 cdiv_nc(f2 a, f2 b) {
+  const float ns = b.x * b.x + b.y * b.y;
+  return f2{(a.x * b.x + a.y * b.y) / ns, (a.y * b.x - a.x * b.y) / ns};
+}
+__device__ __forceinline__ f2 cmul_nc(f2 a, f2 b) { return f2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ f2 eq_weight(f2 h) {
+  const float m = h.x * h.x + h.y * h.y;
+  return m >= ofdm::kEqualizerFloor ? f2{h.x / m, -h.y / m} : f2{0.0f, 0.0f};
+}
+// The estimate at bin from np > 0 bin-sorted pilots; rx(bin) is the received value of a bin.
+// The two bracketing pilots' ratios are computed here, per bin, by binary search as the
+// reference does; no ratio table is kept between bins.
+template <class Rx>
+__device__ __forceinline__ f2 interp_est(const uint32_t* __restrict__ pb, const f2* __restrict__ pv, int np,
+                                         uint32_t bin, Rx rx) {
+  int pick;
+  if (np == 1) {
+    pick = 0;
+  } else {
+    int lo = 0, hi = np;  // the first pilot with pbin >= bin
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (pb[mid] < bin)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (lo == 0) {
+      pick = 0;
+    } else if (lo == np) {
+      pick = np - 1;
+    } else if (pb[lo] == bin) {
+      pick = lo;
+    } else {
+      const f2 lr = cdiv_nc(rx(pb[lo - 1]), pv[lo - 1]), ur = cdiv_nc(rx(pb[lo]), pv[lo]);
+      const float t = static_cast<float>(bin - pb[lo - 1]) / static_cast<float>(pb[lo] - pb[lo - 1]);
+      return f2{lr.x + (ur.x - lr.x) * t, lr.y + (ur.y - lr.y) * t};
+    }
+  }
+  return cdiv_nc(rx(pb[pick]), pv[pick]);
+}
+}  // namespace
+
+// ---- k_fft ------------------------------------------------------------------------------
+__global__ __launch_bounds__(kOfdmThreads) void k_fft(const f2* __restrict__ in, long long in_stride,
+                                                      f2* __restrict__ out, long long out_stride, long long batch,
+                                                      int n, int log2n, int T, const f2* __restrict__ tw, int inverse) {
+  extern __shared__ f2 lds[];
+  const int tid = threadIdx.x, sl = tid / T, t = tid - sl * T;
+  const long long sym = static_cast<long long>(blockIdx.x) * (kOfdmThreads / T) + sl;
+  const bool valid = sym < batch;
+  f2* x = lds + sl * (n + (n >> 5));
+  for (int i = t; i < n; i += T) x[pad(brev(i, log2n))] = valid ? in[sym * in_stride + i] : f2{0.0f, 0.0f};
+  fft_lds(x, n, log2n, tw, inverse != 0, t, T);
+  if (!valid) return;
+  const float g = 1.0f / static_cast<float>(n);
+  for (int k = t; k < n; k += T) {
+    f2 v = x[pad(k)];
+    if (inverse) v = f2{v.x * g, v.y * g};
+    out[sym * out_stride + k] = v;
+  }
+}
+
+// ---- k_ofdm_mod -------------------------------------------------------------------------
+// bits [batch][nd * bps] u8 -> out [batch][n + cp] cf32; batch = channels x symbols.
+__global__ __launch_bounds__(kOfdmThreads) void k_ofdm_mod(const uint8_t* __restrict__ bits, f2* __restrict__ out,
+                                                           long long batch, OfdmDev c, float gain, int apply_gain) {
+  extern __shared__ f2 lds[];
+  const int n = c.n, T = c.T;
+  const int tid = threadIdx.x, sl = tid / T, t = tid - sl * T;
+  const long long sym = static_cast<long long>(blockIdx.x) * (kOfdmThreads / T) + sl;
+  const bool valid = sym < batch;
+  f2* x = lds + sl * (n + (n >> 5));
+  const uint8_t* b = bits + sym * (static_cast<long long>(c.nd) * c.bps);
+  for (int bin = t; bin < n; bin += T) {  // GridMap as a gather: data, pilot or null per bin
+    f2 v{0.0f, 0.0f};
+    if (valid) {
+      const int m = c.map[bin];
+      if (m >= 0)
+        v = map_point(c.order, b + static_cast<long long>(m) * c.bps, c.axis);
+      else if (m <= -2)
+        v = c.pilot_val[-2 - m];
+    }
+    x[pad(brev(bin, c.log2n))] = v;
+  }
+  fft_lds(x, n, c.log2n, c.tw, true, t, T);
+  if (!valid) return;
+  const float s = 1.0f / static_cast<float>(n);
+  const int len = n + c.cp;
+  for (int i = t; i < len; i += T) {
+    const int m = i < c.cp ? n - c.cp + i : i - c.cp;  // CyclicPrefixInsert
+    f2 v = x[pad(m)];
+    v = f2{v.x * s, v.y * s};
+    if (i < c.roll) {  // SymbolWindow: both edges
+      const float w = c.ramp[i];
+      v = f2{v.x * w, v.y * w};
+    }
+    if (len - 1 - i < c.roll) {
+      const float w = c.ramp[len - 1 - i];
+      v = f2{v.x * w, v.y * w};
+    }
+    if (apply_gain) v = f2{gain * v.x, gain * v.y};
+    out[sym * len + i] = v;
+  }
+}
+
+// The RF stage (modulate/ofdm.rs:525-532) in place: iq [nch][per_ch], channel sample j takes
+// oscillator output k0 + j: g fma(s.re, r.re, -(s.im r.im)), g fma(s.im, r.re, s.re r.im).
+__global__ __launch_bounds__(256) void k_ofdm_rf(f2* __restrict__ iq, long long per_ch, long long total, uint64_t k0,
+                                                 OscDev o, float gain) {
+  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= total) return;
+  const f2 r = osc_at(o, k0 + static_cast<uint64_t>(i % per_ch));
+  const f2 v = cmul_rot(iq[i], r);
+  iq[i] = f2{gain * v.x, gain * v.y};
+}
+
+// ---- k_ofdm_demod -----------------------------------------------------------------------
+// iq [batch][n + cp] -> soft [batch][nd] cf32, and from the same values bits [batch][nd * bps]
+// u8 and llr [batch][nd * bps] f32 where asked for. eq: ofdm::kEqNone, kEqTrainingSymbolHold
+// (c.weight) or kEqPerSymbolPilotInterp (the bin-sorted pilots; c.hold with no pilot).
+__global__ __launch_bounds__(kOfdmThreads) void k_ofdm_demod(const f2* __restrict__ iq, f2* __restrict__ soft,
+                                                             uint8_t* __restrict__ bits, float* __restrict__ llr,
+                                                             long long batch, OfdmDev c, int start, float gain,
+                                                             int apply_gain, int eq) {
+  extern __shared__ f2 lds[];
+  const int n = c.n, T = c.T;
+  const int tid = threadIdx.x, sl = tid / T, t = tid - sl * T;
+  const long long sym = static_cast<long long>(blockIdx.x) * (kOfdmThreads / T) + sl;
+  const bool valid = sym < batch;
+  f2* x = lds + sl * (n + (n >> 5));
+  const f2* src = iq + sym * (n + c.cp) + start;
+  for (int i = t; i < n; i += T) x[pad(brev(i, c.log2n))] = valid ? src[i] : f2{0.0f, 0.0f};
+  fft_lds(x, n, c.log2n, c.tw, false, t, T);
+  if (!valid) return;
+  auto rx = [x](uint32_t bin) { return x[pad(static_cast<int>(bin))]; };
+  for (int d = t; d < c.nd; d += T) {
+    const uint32_t bin = c.data_bins[d];
+    f2 v = rx(bin);
+    if (eq == ofdm::kEqTrainingSymbolHold) {
+      v = cmul_nc(v, c.weight[bin]);
+    } else if (eq == ofdm::kEqPerSymbolPilotInterp) {
+      const f2 h = c.np > 0 ? interp_est(c.spbin, c.spval, c.np, bin, rx) : c.hold[bin];
+      v = cmul_nc(v, eq_weight(h));
+    }
+    if (apply_gain) v = f2{gain * v.x, gain * v.y};
+    const long long o = sym * c.nd + d;
+    soft[o] = v;
+    if (bits) decide_sym(c.order, v, c.thr, bits + o * c.bps);
+    if (llr) llr_sym(c.order, v, c.axis, llr + o * c.bps);
+  }
+}
+
+// ---- the elementwise blocks -------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ofdm_decide(const f2* __restrict__ soft, long long n, int order, int bps,
+                                                     const float* __restrict__ thr, uint8_t* __restrict__ bits) {
+  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i < n) decide_sym(order, soft[i], thr, bits + i * bps);
+}
+__global__ __launch_bounds__(256) void k_ofdm_llr(const f2* __restrict__ soft, long long n, int order, int bps,
+                                                  const float* __restrict__ axis, float* __restrict__ llr) {
+  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i < n) llr_sym(order, soft[i], axis, llr + i * bps);
+}
+// OfdmEqualizer::process over nsym n-bin vectors. emap (kEqPerSymbolPilotInterp with pilots):
+// 0 the held estimate, 1 a data bin (interpolated), 2 + p the bin of sorted pilot p (its own ratio).
+__global__ __launch_bounds__(256) void k_ofdm_equalize(const f2* __restrict__ in, f2* __restrict__ out, long long nsym,
+                                                       OfdmDev c, int eq) {
+  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= nsym * c.n) return;
+  const long long sym = i / c.n;
+  const uint32_t bin = static_cast<uint32_t>(i - sym * c.n);
+  const f2* row = in + sym * c.n;
+  auto rx = [row](uint32_t b) { return row[b]; };
+  f2 w;
+  if (eq == ofdm::kEqTrainingSymbolHold) {
+    w = c.weight[bin];
+  } else {
+    f2 h = c.hold[bin];
+    if (c.np > 0) {
+      const int role = c.emap[bin];
+      if (role == 1)
+        h = interp_est(c.spbin, c.spval, c.np, bin, rx);
+      else if (role >= 2)
+        h = cdiv_nc(row[bin], c.spval[role - 2]);
+    }
+    w = eq_weight(h);
+  }
+  out[i] = cmul_nc(row[bin], w);
+}
+
+// ---- launchers --------------------------------------------------------------------------
+namespace {
+unsigned sym_grid(long long batch, int T) {
+  const long long per = kOfdmThreads / T, g = (batch + per - 1) / per;
+  if (g > 0x7fffffffLL) throw std::invalid_argument("ofdm: too many symbols for one launch");
+  return static_cast<unsigned>(g);
+}
+size_t sym_lds(int n, int T) { return static_cast<size_t>(kOfdmThreads / T) * (n + (n >> 5)) * sizeof(f2); }
+unsigned flat_grid(long long total) {
+  const long long g = (total + 255) / 256;
+  if (g > 0x7fffffffLL) throw std::invalid_argument("ofdm: too many values for one launch");
+  return static_cast<unsigned>(g);
+}
+}  // namespace
+
+int ofdm_threads_per_symbol(size_t n) { return static_cast<int>(std::min<size_t>(n / 4, kOfdmThreads)); }
+
+void launch_fft(const f2* in, long long in_stride, f2* out, long long out_stride, long long batch, int n, int log2n,
+                const f2* tw, bool inverse, hipStream_t s) {
+  if (batch < 1) return;
+  const int T = ofdm_threads_per_symbol(n);
+  k_fft<<<sym_grid(batch, T), kOfdmThreads, sym_lds(n, T), s>>>(in, in_stride, out, out_stride, batch, n, log2n, T, tw,
+                                                               inverse ? 1 : 0);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_mod(const uint8_t* bits, f2* out, long long batch, const OfdmDev& c, float gain, bool apply_gain,
+                     hipStream_t s) {
+  if (batch < 1) return;
+  k_ofdm_mod<<<sym_grid(batch, c.T), kOfdmThreads, sym_lds(c.n, c.T), s>>>(bits, out, batch, c, gain, apply_gain ? 1 : 0);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_rf(f2* iq, long long per_ch, long long nch, uint64_t k0, const OscDev& o, float gain, hipStream_t s) {
+  const long long total = per_ch * nch;
+  if (total < 1) return;
+  k_ofdm_rf<<<flat_grid(total), 256, 0, s>>>(iq, per_ch, total, k0, o, gain);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_demod(const f2* iq, f2* soft, uint8_t* bits, float* llr, long long batch, const OfdmDev& c, int start,
+                       float gain, bool apply_gain, int eq, hipStream_t s) {
+  if (batch < 1) return;
+  k_ofdm_demod<<<sym_grid(batch, c.T), kOfdmThreads, sym_lds(c.n, c.T), s>>>(iq, soft, bits, llr, batch, c, start, gain,
+                                                                          apply_gain ? 1 : 0, eq);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_decide(const f2* soft, long long n, int order, const float* thr, uint8_t* bits, hipStream_t s) {
+  if (n < 1) return;
+  k_ofdm_decide<<<flat_grid(n), 256, 0, s>>>(soft, n, order, static_cast<int>(ofdm::bits_per_symbol(order)), thr, bits);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_llr(const f2* soft, long long n, int order, const float* axis, float* llr, hipStream_t s) {
+  if (n < 1) return;
+  k_ofdm_llr<<<flat_grid(n), 256, 0, s>>>(soft, n, order, static_cast<int>(ofdm::bits_per_symbol(order)), axis, llr);
+  ORION_LAUNCH_CHECK();
+}
+void launch_ofdm_equalize(const f2* in, f2* out, long long nsym, const OfdmDev& c, int eq, hipStream_t s) {
+  if (nsym < 1) return;
+  k_ofdm_equalize<<<flat_grid(nsym * c.n), 256, 0, s>>>(in, out, nsym, c, eq);
+  ORION_LAUNCH_CHECK();
+}
+
+}  // namespace orion

@@ -41,6 +41,10 @@ __all__ = [
     "PSK31_TRACEBACK_DEPTH", "psk31_sps", "psk31_text_bits", "Bpsk31Mod", "Qpsk31Mod", "Bpsk31Demod", "Qpsk31Demod",
     "Bpsk31Decider", "Psk31DemodBank", "PSK31_STREAM_DTYPE", "PSK31_REPORT_DTYPE", "psk31_find_carriers", "psk31_find_carriers_device", "psk31_synth", "PSK31_SIGNAL_DTYPE", "psk31_rotator_q64",
     "psk31_sync", "psk31_sync_batch", "best_psk31_sync", "psk31_decode", "psk31_decode_batch", "Psk31Stream",
+    "OfdmConfig", "OfdmMod", "OfdmDemod", "OfdmDecider", "OfdmSoftDemod", "OfdmEqualizer", "OfdmRxFrame",
+    "build_ofdm_rx_frame", "FftBlock", "IfftBlock", "ofdm_modulate_batch", "ofdm_demodulate_batch", "ofdm_tables",
+    "ofdm_map", "ofdm_decide", "ofdm_llr", "fft_host", "ofdm_window", "ofdm_rotator", "ofdm_equalizer_weight",
+    "ofdm_interpolate", "ofdm_max_pilot_safe_backoff", "OFDM_CONSTELLATIONS", "OFDM_PLAN_ERRORS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -2389,3 +2393,691 @@ def device_count() -> int:
 
 def version() -> str:
     return _L.orion_version().decode()
+
+
+# ---- the OFDM symbol layer (src/multicarrier, modulate/ofdm.rs, demodulate/ofdm.rs; src/python/ofdm.rs) ----
+def _ofdm_sigs():
+    vp, sz, f, i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
+    wr = C.POINTER(WorkReport)
+    sig = {
+        "orion_ofdm_config_new": (vp, [sz, sz, vp, sz, vp, vp, sz, f, f, f, i]),
+        "orion_ofdm_config_free": (None, [vp]),
+        "orion_ofdm_config_contiguous_data": (i, [vp, sz, i]),
+        "orion_ofdm_config_set_rx_window_backoff": (i, [vp, sz]),
+        "orion_ofdm_config_set_symbol_window": (i, [vp, sz]),
+        "orion_ofdm_config_validate": (i, [vp, C.c_longlong, C.POINTER(C.c_int32)]),
+        "orion_ofdm_config_info": (i, [vp, C.POINTER(sz)]),
+        "orion_ofdm_config_data_carriers": (i, [vp, vp, sz]),
+        "orion_ofdm_config_occupied_bins": (i, [vp, vp, sz, C.POINTER(sz)]),
+        "orion_ofdm_config_grid": (i, [vp, vp, vp]),
+        "orion_ofdm_max_pilot_safe_backoff": (sz, [sz, sz]),
+        "orion_ofdm_tables": (i, [i, vp, vp, sz, vp, vp, sz, sz, vp]),
+        "orion_ofdm_map_host": (i, [i, vp, sz, vp]), "orion_ofdm_decide_host": (i, [i, vp, sz, vp]),
+        "orion_ofdm_llr_host": (i, [i, vp, sz, vp]), "orion_fft_host": (i, [sz, i, vp, sz, vp]),
+        "orion_ofdm_window_host": (i, [sz, sz, vp, sz]), "orion_ofdm_rotator_host": (i, [f, f, sz, vp]),
+        "orion_ofdm_evm_db_host": (i, [i, vp, sz, vp, sz, sz, C.POINTER(f), C.POINTER(i)]),
+        "orion_ofdm_equalizer_weight_host": (i, [vp, sz, vp]),
+        "orion_ofdm_interpolate_host": (i, [vp, vp, sz, vp, sz, vp]),
+        "orion_fft_new": (vp, [sz]), "orion_ifft_new": (vp, [sz]), "orion_fft_free": (None, [vp]),
+        "orion_fft_process": (i, [vp, vp, sz, vp, sz, wr]),
+        "orion_fft_batch": (i, [vp, vp, sz, vp, sz, sz, vp]),
+        "orion_ofdm_mod_new": (vp, [vp]), "orion_ofdm_demod_new": (vp, [vp, i]),
+        "orion_ofdm_decider_new": (vp, [vp]), "orion_ofdm_soft_demod_new": (vp, [vp]),
+        "orion_ofdm_equalizer_new": (vp, [vp, i]), "orion_ofdm_free": (None, [vp]),
+        "orion_ofdm_set_gain": (i, [vp, f]), "orion_ofdm_reset": (i, [vp]),
+        "orion_ofdm_estimate_channel": (i, [vp, vp, sz]),
+        "orion_ofdm_process": (i, [vp, vp, sz, vp, sz, wr]),
+        "orion_ofdm_mod_device": (i, [vp, vp, sz, sz, vp, vp]),
+        "orion_ofdm_demod_device": (i, [vp, vp, sz, sz, vp, vp, vp, vp]),
+        "orion_ofdm_decider_device": (i, [vp, vp, sz, sz, vp, vp]),
+        "orion_ofdm_soft_demod_device": (i, [vp, vp, sz, sz, vp, vp]),
+        "orion_ofdm_equalizer_device": (i, [vp, vp, sz, sz, vp, vp]),
+        "orion_ofdm_mod_host": (i, [vp, vp, sz, vp, sz, wr]), "orion_ofdm_demod_host": (i, [vp, vp, sz, vp, sz, wr]),
+        "orion_ofdm_equalize_host": (i, [vp, vp, sz, vp, sz, wr]),
+        "orion_ofdm_set_pilot_bins_host": (i, [vp, vp, vp, sz, vp, sz]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_ofdm_sigs()
+
+OFDM_CONSTELLATIONS = {"bpsk": 0, "qpsk": 1, "qam16": 2, "qam64": 3, "qam256": 4}  # src/python/ofdm.rs:29-41
+OFDM_PLAN_ERRORS = {1: "out_of_range", 2: "overlap", 3: "empty_data_set", 4: "in_guard_band"}  # config.rs:17-26
+_OFDM_EQ = {None: -1, "training_symbol": 0, "pilot_interp": 1}  # src/python/ofdm.rs:532-541
+
+
+def _ofdm_arr(x, dtype, name):
+    """1-D contiguous input of exactly this dtype (src/python/ofdm.rs takes PyReadonlyArray1 slices)."""
+    if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 1 or not x.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{name}: expected a 1-D contiguous {np.dtype(dtype).name} array")
+    return x
+
+
+def _ofdm_order(constellation) -> int:
+    if constellation not in OFDM_CONSTELLATIONS:
+        raise ValueError(f"unknown constellation {constellation!r} (expected one of {sorted(OFDM_CONSTELLATIONS)})")
+    return OFDM_CONSTELLATIONS[constellation]
+
+
+def ofdm_max_pilot_safe_backoff(n_fft: int, pilot_spacing: int) -> int:
+    """SymbolFft::max_pilot_safe_backoff (symbol_fft.rs:90-92)."""
+    return int(_L.orion_ofdm_max_pilot_safe_backoff(int(n_fft), int(pilot_spacing)))
+
+
+def ofdm_tables(constellation="qam16", n_fft=0, symbol_len=0, roll_off=0):
+    """(axis float32 (16,), thresholds float32 (15,), training complex64 (n_fft,), twiddles
+    complex64 (n_fft // 2,), ramp float32) as the library holds them (modulate/qam.rs:27-57,
+    demodulate/qam.rs:28-41, sync/ofdm_sync.rs:270-352, symbol_window.rs:47-59), host only."""
+    axis, thr = np.zeros(16, np.float32), np.zeros(15, np.float32)
+    tr, tw = np.zeros(int(n_fft), np.complex64), np.zeros(int(n_fft) // 2, np.complex64)
+    ramp = np.zeros(min(int(roll_off), int(symbol_len) // 2), np.float32)
+    _arg_check(_L.orion_ofdm_tables(_ofdm_order(constellation), axis.ctypes.data, thr.ctypes.data, int(n_fft),
+                                    tr.ctypes.data if n_fft else None, tw.ctypes.data if n_fft else None,
+                                    int(symbol_len), int(roll_off), ramp.ctypes.data if ramp.size else None))
+    return axis, thr, tr, tw, ramp
+
+
+def ofdm_map(constellation, bits) -> np.ndarray:
+    """The symbol mapper of an order on the host: uint8 bits -> complex64 symbols."""
+    bits = _ofdm_arr(bits, np.uint8, "bits")
+    order = _ofdm_order(constellation)
+    n = bits.size // (1, 2, 4, 6, 8)[order]
+    out = np.zeros(n, np.complex64)
+    _arg_check(_L.orion_ofdm_map_host(order, bits.ctypes.data, n, out.ctypes.data))
+    return out
+
+
+def ofdm_decide(constellation, syms) -> np.ndarray:
+    """The hard decider of an order on the host: complex64 symbols -> uint8 bits."""
+    syms = _ofdm_arr(syms, np.complex64, "syms")
+    order = _ofdm_order(constellation)
+    out = np.zeros(syms.size * (1, 2, 4, 6, 8)[order], np.uint8)
+    _arg_check(_L.orion_ofdm_decide_host(order, syms.ctypes.data, syms.size, out.ctypes.data))
+    return out
+
+
+def ofdm_llr(constellation, syms) -> np.ndarray:
+    """The max-log LLRs of an order on the host (positive = 0): complex64 symbols -> float32."""
+    syms = _ofdm_arr(syms, np.complex64, "syms")
+    order = _ofdm_order(constellation)
+    out = np.zeros(syms.size * (1, 2, 4, 6, 8)[order], np.float32)
+    _arg_check(_L.orion_ofdm_llr_host(order, syms.ctypes.data, syms.size, out.ctypes.data))
+    return out
+
+
+def fft_host(x, n_fft: int, inverse: bool = False) -> np.ndarray:
+    """The library's scalar radix-2 transform of every whole n_fft-point symbol of x (host only)."""
+    x = _ofdm_arr(x, np.complex64, "x")
+    n_fft = int(n_fft)
+    k = x.size // n_fft if n_fft > 0 else 0
+    out = np.zeros(k * n_fft, np.complex64)
+    _arg_check(_L.orion_fft_host(n_fft, int(bool(inverse)), x.ctypes.data, k, out.ctypes.data))
+    return out
+
+
+def ofdm_window(iq, symbol_len: int, roll_off: int) -> np.ndarray:
+    """SymbolWindow (symbol_window.rs:80-98) over every whole symbol of iq, host only."""
+    iq = _ofdm_arr(iq, np.complex64, "iq").copy()
+    if symbol_len > 0:
+        _arg_check(_L.orion_ofdm_window_host(int(symbol_len), int(roll_off), iq.ctypes.data, iq.size // int(symbol_len)))
+    return iq
+
+
+def ofdm_rotator(freq_hz: float, fs: float, n: int) -> np.ndarray:
+    """Rotator(freq_hz, fs).next() n times from a fresh oscillator (dsp/rotator.rs:16-61), host only."""
+    out = np.zeros(int(n), np.complex64)
+    _check(_L.orion_ofdm_rotator_host(float(freq_hz), float(fs), out.size, out.ctypes.data))
+    return out
+
+
+def ofdm_equalizer_weight(h) -> np.ndarray:
+    """equalizer_weight (demodulate/ofdm.rs:495-502) of each estimate, host only."""
+    h = _ofdm_arr(h, np.complex64, "h")
+    out = np.zeros(h.size, np.complex64)
+    _check(_L.orion_ofdm_equalizer_weight_host(h.ctypes.data, h.size, out.ctypes.data))
+    return out
+
+
+def ofdm_interpolate(pilot_bins, ratios, bins) -> np.ndarray:
+    """interpolate_at (demodulate/ofdm.rs:514-537) over bin-sorted pilot ratios, host only."""
+    pb = np.ascontiguousarray(pilot_bins, np.uint32)
+    r = _ofdm_arr(ratios, np.complex64, "ratios")
+    b = np.ascontiguousarray(bins, np.uint32)
+    if pb.size != r.size:
+        raise ValueError("one ratio per pilot bin")
+    out = np.zeros(b.size, np.complex64)
+    _arg_check(_L.orion_ofdm_interpolate_host(pb.ctypes.data, r.ctypes.data, pb.size, b.ctypes.data, b.size,
+                                              out.ctypes.data))
+    return out
+
+
+class OfdmConfig:
+    """OfdmConfig (src/python/ofdm.rs:50-130 over modulate/ofdm.rs:57-365): the carrier plan,
+    sample rate, carrier, gain and constellation. With edge_guard the data carriers are the
+    contiguous span of with_contiguous_data(edge_guard, False) and data_carriers must be empty.
+    Raises ValueError as the reference does (validate), and for what this library does not
+    take: an n_fft that is not a power of two from 8 to 4096, or cp_len > n_fft."""
+
+    def __init__(self, n_fft, cp_len, data_carriers, pilot_carrier_indices, pilot_carrier_values, fs, rf_hz, gain,
+                 constellation, edge_guard=None):
+        data = _ofdm_arr(np.asarray(data_carriers), np.int32, "data_carriers") if not isinstance(data_carriers, np.ndarray) \
+            else _ofdm_arr(data_carriers, np.int32, "data_carriers")
+        pidx = _ofdm_arr(pilot_carrier_indices, np.int32, "pilot_carrier_indices")
+        pval = _ofdm_arr(pilot_carrier_values, np.complex64, "pilot_carrier_values")
+        if pidx.size != pval.size:
+            raise ValueError(f"OfdmConfig: pilot_carrier_indices ({pidx.size}) and pilot_carrier_values ({pval.size}) "
+                             "must have the same length")
+        order = _ofdm_order(constellation)
+        n_fft, cp_len = int(n_fft), int(cp_len)
+        if n_fft < 8 or n_fft > 4096 or n_fft & (n_fft - 1):
+            raise ValueError(f"OfdmConfig: n_fft {n_fft} is not a power of two from 8 to 4096")
+        if cp_len < 0 or cp_len > n_fft:
+            raise ValueError(f"OfdmConfig: cp_len {cp_len} outside 0..n_fft")
+        if edge_guard is not None and data.size:
+            raise ValueError("OfdmConfig: pass an empty data_carriers array when edge_guard is set "
+                             "(the contiguous span is generated automatically)")
+        self._h = _L.orion_ofdm_config_new(n_fft, cp_len, data.ctypes.data, data.size, pidx.ctypes.data,
+                                           pval.ctypes.data, pidx.size, float(fs), float(rf_hz), float(gain), order)
+        if not self._h:
+            raise OrionError(f"orion_sdr: construction failed: {_err()}")
+        if edge_guard is not None:
+            _arg_check(_L.orion_ofdm_config_contiguous_data(self._h, int(edge_guard), 0))
+        bad = C.c_int32(0)
+        rc = _L.orion_ofdm_config_validate(self._h, -1, C.byref(bad))
+        if rc > 0:
+            raise ValueError(f"OfdmConfig: carrier plan error {OFDM_PLAN_ERRORS[rc]} (carrier index {bad.value})")
+        _check(rc)
+        self._args = (n_fft, cp_len, pidx.copy(), pval.copy(), float(fs), float(rf_hz), float(gain), constellation)
+        self.constellation = constellation
+        self.fs, self.rf_hz, self.gain = float(fs), float(rf_hz), float(gain)
+        self.rx_window_backoff = 0
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.orion_ofdm_config_free(h)
+            self._h = None
+
+    def _info(self):
+        a = (C.c_size_t * 8)()
+        _check(_L.orion_ofdm_config_info(self._h, a))
+        return [int(v) for v in a]
+
+    n_fft = property(lambda self: self._info()[0])
+    cp_len = property(lambda self: self._info()[1])
+    num_data_carriers = property(lambda self: self._info()[2])
+    bits_per_ofdm_symbol = property(lambda self: self._info()[4])
+    samples_per_ofdm_symbol = property(lambda self: self._info()[5])
+    occupied_half_carriers = property(lambda self: self._info()[6])
+    window_roll_off = property(lambda self: self._info()[7])
+
+    @property
+    def data_carriers(self) -> np.ndarray:
+        out = np.zeros(self._info()[2], np.int32)
+        _check(_L.orion_ofdm_config_data_carriers(self._h, out.ctypes.data, out.size))
+        return out
+
+    def occupied_bins(self) -> np.ndarray:
+        """occupied_bins (config.rs:188-203)."""
+        out = np.zeros(self._info()[0], np.uint32)
+        n = C.c_size_t(0)
+        _check(_L.orion_ofdm_config_occupied_bins(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out[: n.value].copy()
+
+    def grid(self):
+        """CarrierGrid::from_plan (grid.rs:40-66): (data_bins, pilot_bins) uint32."""
+        i = self._info()
+        d, p = np.zeros(i[2], np.uint32), np.zeros(i[3], np.uint32)
+        _arg_check(_L.orion_ofdm_config_grid(self._h, d.ctypes.data, p.ctypes.data))
+        return d, p
+
+    def validate_edge_guard(self, edge_guard: int):
+        """validate_edge_guard (config.rs:262-278): raises ValueError where it fails."""
+        bad = C.c_int32(0)
+        rc = _L.orion_ofdm_config_validate(self._h, int(edge_guard), C.byref(bad))
+        if rc > 0:
+            raise ValueError(f"OfdmConfig: carrier plan error {OFDM_PLAN_ERRORS[rc]} (carrier index {bad.value})")
+        _check(rc)
+
+    def _clone(self):
+        n_fft, cp_len, pidx, pval, fs, rf, g, con = self._args
+        c = OfdmConfig(n_fft, cp_len, self.data_carriers, pidx, pval, fs, rf, g, con)
+        _check(_L.orion_ofdm_config_set_rx_window_backoff(c._h, self.rx_window_backoff))
+        c.rx_window_backoff = self.rx_window_backoff
+        _check(_L.orion_ofdm_config_set_symbol_window(c._h, self.window_roll_off))
+        return c
+
+    def with_rx_window_backoff(self, backoff: int) -> "OfdmConfig":
+        """with_rx_window_backoff (modulate/ofdm.rs:240-243): a new configuration."""
+        if backoff < 0:
+            raise ValueError("backoff must be >= 0")
+        c = self._clone()
+        _check(_L.orion_ofdm_config_set_rx_window_backoff(c._h, int(backoff)))
+        c.rx_window_backoff = int(backoff)
+        return c
+
+    def with_symbol_window(self, roll_off: int) -> "OfdmConfig":
+        """with_symbol_window (modulate/ofdm.rs:256-259): a new configuration."""
+        if roll_off < 0:
+            raise ValueError("roll_off must be >= 0")
+        c = self._clone()
+        _check(_L.orion_ofdm_config_set_symbol_window(c._h, int(roll_off)))
+        return c
+
+
+def _torch_1d(x, dtype_name, name):
+    import torch
+
+    if not x.is_cuda or not x.is_contiguous() or x.dim() != 1 or x.dtype != getattr(torch, dtype_name):
+        raise ValueError(f"{name}: expected a 1-D contiguous {dtype_name} CUDA tensor")
+    return x
+
+
+class _FftBase:
+    _inverse = False
+
+    def __init__(self, n_fft: int):
+        n_fft = int(n_fft)
+        if n_fft < 8 or n_fft > 4096 or n_fft & (n_fft - 1):
+            raise ValueError(f"{type(self).__name__}: n_fft {n_fft} is not a power of two from 8 to 4096")
+        self._h = (_L.orion_ifft_new if self._inverse else _L.orion_fft_new)(n_fft)
+        if not self._h:
+            raise OrionError(f"orion_sdr: construction failed: {_err()}")
+        self.n_fft = n_fft
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.orion_fft_free(h)
+            self._h = None
+
+    def process(self, x):
+        """One n_fft-point symbol per call, as the reference block (fft.rs:42-54): the first
+        n_fft values are transformed; a shorter input gives an empty array. numpy complex64
+        in and out; a torch CUDA tensor stays resident."""
+        if _is_torch(x):
+            import torch
+
+            x = _torch_1d(x, "complex64", "x")
+            if x.numel() < self.n_fft:
+                return torch.empty(0, dtype=torch.complex64, device=x.device)
+            return self.process_batch(x[: self.n_fft].reshape(1, self.n_fft)).reshape(self.n_fft)
+        x = _ofdm_arr(x, np.complex64, "x")
+        out = np.zeros(self.n_fft, np.complex64)
+        wr = WorkReport()
+        _arg_check(_L.orion_fft_process(self._h, x.ctypes.data, x.size, out.ctypes.data, out.size, C.byref(wr)))
+        return out[: wr.out_written]
+
+    def process_batch(self, x, stream=None):
+        """(batch, n_fft) symbols in one launch. A torch CUDA complex64 tensor whose rows are
+        contiguous (any row stride >= n_fft, so a window of longer symbols may be passed as a
+        view) stays resident; a numpy array costs one upload and one download."""
+        import torch
+
+        if not _is_torch(x):
+            if not isinstance(x, np.ndarray) or x.dtype != np.complex64 or x.ndim != 2 or x.shape[1] != self.n_fft:
+                raise ValueError(f"x: expected a (batch, {self.n_fft}) complex64 array")
+            return self.process_batch(torch.from_numpy(np.ascontiguousarray(x)).cuda(), stream).cpu().numpy()
+        if not x.is_cuda or x.dtype != torch.complex64 or x.dim() != 2 or x.shape[1] != self.n_fft or \
+                (x.shape[0] > 0 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < self.n_fft):
+            raise ValueError(f"x: expected a (batch, {self.n_fft}) complex64 CUDA tensor with contiguous rows")
+        out = torch.empty((x.shape[0], self.n_fft), dtype=torch.complex64, device=x.device)
+        stride = int(x.stride(0)) if x.shape[0] > 1 else self.n_fft
+        _arg_check(_L.orion_fft_batch(self._h, x.data_ptr(), stride, out.data_ptr(), self.n_fft, int(x.shape[0]),
+                                      SyncEngine._stream(x, stream)))
+        return out
+
+
+class FftBlock(_FftBase):
+    """FftBlock (multicarrier/fft.rs:16-55) on the GPU: forward, unity gain."""
+
+
+class IfftBlock(_FftBase):
+    """IfftBlock (multicarrier/fft.rs:63-120) on the GPU: inverse, times 1 / n_fft."""
+    _inverse = True
+
+
+class _OfdmHandle:
+    def __init__(self, h, cfg: OfdmConfig):
+        if not h:
+            msg = _err()
+            raise ValueError(msg) if "ofdm" in msg else OrionError(f"orion_sdr: construction failed: {msg}")
+        self._h = h
+        self.bits_per_ofdm_symbol = cfg.bits_per_ofdm_symbol
+        self.samples_per_ofdm_symbol = cfg.samples_per_ofdm_symbol
+        self.num_data_carriers = cfg.num_data_carriers
+        self.n_fft, self.cp_len = cfg.n_fft, cfg.cp_len
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.orion_ofdm_free(h)
+            self._h = None
+
+    def _process(self, x, out):
+        wr = WorkReport()
+        _arg_check(_L.orion_ofdm_process(self._h, x.ctypes.data, x.size, out.ctypes.data, out.size, C.byref(wr)))
+        return wr
+
+    def process_into(self, x, out) -> WorkReport:
+        """The Block contract (core.rs:12-22) on the GPU: as many whole symbols as fit in both."""
+        return self._process(_ofdm_arr(x, self._in, "input"), _ofdm_arr(out, self._out, "output"))
+
+    def process_host_into(self, x, out) -> WorkReport:
+        """The same call through the library's scalar host code (no device)."""
+        x, out = _ofdm_arr(x, self._in, "input"), _ofdm_arr(out, self._out, "output")
+        wr = WorkReport()
+        _arg_check(self._host_fn(self._h, x.ctypes.data, x.size, out.ctypes.data, out.size, C.byref(wr)))
+        return wr
+
+
+class OfdmMod(_OfdmHandle):
+    """OfdmMod (modulate/ofdm.rs:422-544; src/python/ofdm.rs) on the GPU: bits -> mapper -> grid
+    -> inverse transform -> cyclic prefix -> optional symbol window -> gain (and the rotator
+    when rf_hz != 0, whose phase carries across calls), one launch for every symbol."""
+    _in, _out = np.uint8, np.complex64
+    _host_fn = staticmethod(lambda *a: _L.orion_ofdm_mod_host(*a))
+
+    def __init__(self, cfg: OfdmConfig):
+        super().__init__(_L.orion_ofdm_mod_new(cfg._h), cfg)
+
+    def set_gain(self, g: float):
+        _check(_L.orion_ofdm_set_gain(self._h, float(g)))
+
+    def reset(self):
+        _check(_L.orion_ofdm_reset(self._h))
+
+    def modulate(self, bits):
+        """modulate (modulate/ofdm.rs:469-493): every bit, the last symbol zero-padded. uint8
+        numpy bits -> numpy complex64; a torch CUDA uint8 tensor stays resident."""
+        bps = self.bits_per_ofdm_symbol
+        if _is_torch(bits):
+            import torch
+
+            bits = _torch_1d(bits, "uint8", "bits")
+            nsym = -(-bits.numel() // bps)
+            if nsym * bps != bits.numel():
+                bits = torch.cat([bits, torch.zeros(nsym * bps - bits.numel(), dtype=torch.uint8, device=bits.device)])
+            return ofdm_modulate_batch(self, bits.reshape(1, -1)).reshape(-1)
+        bits = _ofdm_arr(bits, np.uint8, "bits")
+        nsym = -(-bits.size // bps)
+        padded = np.zeros(nsym * bps, np.uint8)
+        padded[: bits.size] = bits
+        out = np.zeros(nsym * self.samples_per_ofdm_symbol, np.complex64)
+        self._process(padded, out)
+        return out
+
+    def modulate_host(self, bits) -> np.ndarray:
+        """modulate by the library's scalar host code (what the kernels are held to)."""
+        bits = _ofdm_arr(bits, np.uint8, "bits")
+        nsym = -(-bits.size // self.bits_per_ofdm_symbol)
+        padded = np.zeros(nsym * self.bits_per_ofdm_symbol, np.uint8)
+        padded[: bits.size] = bits
+        out = np.zeros(nsym * self.samples_per_ofdm_symbol, np.complex64)
+        self.process_host_into(padded, out)
+        return out
+
+
+class OfdmDecider(_OfdmHandle):
+    """OfdmDecider (demodulate/ofdm.rs:137-166) on the GPU: soft symbols -> hard bits."""
+    _in, _out = np.complex64, np.uint8
+
+    def __init__(self, cfg: OfdmConfig):
+        super().__init__(_L.orion_ofdm_decider_new(cfg._h), cfg)
+        self._order = _ofdm_order(cfg.constellation)
+
+    def process(self, soft):
+        if _is_torch(soft):
+            import torch
+
+            soft = _torch_1d(soft, "complex64", "soft")
+            k = soft.numel() // self.num_data_carriers
+            out = torch.empty(k * self.bits_per_ofdm_symbol, dtype=torch.uint8, device=soft.device)
+            _arg_check(_L.orion_ofdm_decider_device(self._h, soft.data_ptr(), 1, k, out.data_ptr(),
+                                                    SyncEngine._stream(soft, None)))
+            return out
+        soft = _ofdm_arr(soft, np.complex64, "soft")
+        out = np.zeros(soft.size // self.num_data_carriers * self.bits_per_ofdm_symbol, np.uint8)
+        self._process(soft, out)
+        return out
+
+    def process_host(self, soft) -> np.ndarray:
+        soft = _ofdm_arr(soft, np.complex64, "soft")
+        k = soft.size // self.num_data_carriers
+        return ofdm_decide(self._constellation_name(), soft[: k * self.num_data_carriers])
+
+    def _constellation_name(self):
+        return [k for k, v in OFDM_CONSTELLATIONS.items() if v == self._order][0]
+
+
+class OfdmSoftDemod(_OfdmHandle):
+    """OfdmSoftDemod (demodulate/ofdm.rs:693-731) on the GPU: soft symbols -> max-log LLRs."""
+    _in, _out = np.complex64, np.float32
+
+    def __init__(self, cfg: OfdmConfig):
+        super().__init__(_L.orion_ofdm_soft_demod_new(cfg._h), cfg)
+        self._constellation = cfg.constellation
+
+    def process(self, soft):
+        if _is_torch(soft):
+            import torch
+
+            soft = _torch_1d(soft, "complex64", "soft")
+            k = soft.numel() // self.num_data_carriers
+            out = torch.empty(k * self.bits_per_ofdm_symbol, dtype=torch.float32, device=soft.device)
+            _arg_check(_L.orion_ofdm_soft_demod_device(self._h, soft.data_ptr(), 1, k, out.data_ptr(),
+                                                       SyncEngine._stream(soft, None)))
+            return out
+        soft = _ofdm_arr(soft, np.complex64, "soft")
+        out = np.zeros(soft.size // self.num_data_carriers * self.bits_per_ofdm_symbol, np.float32)
+        self._process(soft, out)
+        return out
+
+    def process_host(self, soft) -> np.ndarray:
+        soft = _ofdm_arr(soft, np.complex64, "soft")
+        k = soft.size // self.num_data_carriers
+        return ofdm_llr(self._constellation, soft[: k * self.num_data_carriers])
+
+
+class OfdmEqualizer(_OfdmHandle):
+    """OfdmEqualizer (demodulate/ofdm.rs:333-569) on the GPU over whole n_fft-bin vectors:
+    method "training_symbol" (estimate once, hold) or "pilot_interp" (per symbol, linear
+    between the pilots, by binary search per bin)."""
+    _in, _out = np.complex64, np.complex64
+    _host_fn = staticmethod(lambda *a: _L.orion_ofdm_equalize_host(*a))
+
+    def __init__(self, cfg: OfdmConfig, method: str = "training_symbol"):
+        if method not in ("training_symbol", "pilot_interp"):
+            raise ValueError(f"OfdmEqualizer: unknown method {method!r} (expected 'training_symbol' or 'pilot_interp')")
+        super().__init__(_L.orion_ofdm_equalizer_new(cfg._h, _OFDM_EQ[method]), cfg)
+        self.method = method
+
+    def estimate_from_training_symbol(self, received_freq):
+        """estimate_from_training_symbol (demodulate/ofdm.rs:440-448): n_fft received bins."""
+        r = _ofdm_arr(received_freq, np.complex64, "received_freq")
+        _arg_check(_L.orion_ofdm_estimate_channel(self._h, r.ctypes.data, r.size))
+
+    def set_pilot_bins(self, pilot_bins, pilot_values, data_bins):
+        """set_pilot_bins (demodulate/ofdm.rs:426-432)."""
+        pb, db = np.ascontiguousarray(pilot_bins, np.uint32), np.ascontiguousarray(data_bins, np.uint32)
+        pv = _ofdm_arr(pilot_values, np.complex64, "pilot_values")
+        if pb.size != pv.size:
+            raise ValueError("one value per pilot bin")
+        _arg_check(_L.orion_ofdm_set_pilot_bins_host(self._h, pb.ctypes.data, pv.ctypes.data, pb.size, db.ctypes.data,
+                                                     db.size))
+
+    def process(self, freq):
+        if _is_torch(freq):
+            import torch
+
+            freq = _torch_1d(freq, "complex64", "freq")
+            k = freq.numel() // self.n_fft
+            out = torch.empty(k * self.n_fft, dtype=torch.complex64, device=freq.device)
+            _arg_check(_L.orion_ofdm_equalizer_device(self._h, freq.data_ptr(), 1, k, out.data_ptr(),
+                                                      SyncEngine._stream(freq, None)))
+            return out
+        freq = _ofdm_arr(freq, np.complex64, "freq")
+        out = np.zeros(freq.size // self.n_fft * self.n_fft, np.complex64)
+        self._process(freq, out)
+        return out
+
+    def process_host(self, freq) -> np.ndarray:
+        freq = _ofdm_arr(freq, np.complex64, "freq")
+        out = np.zeros(freq.size // self.n_fft * self.n_fft, np.complex64)
+        self.process_host_into(freq, out)
+        return out
+
+
+class OfdmDemod(_OfdmHandle):
+    """OfdmDemod (demodulate/ofdm.rs:26-95 with SymbolFft's window back-off; src/python/ofdm.rs:
+    506-631) on the GPU: window select -> forward transform -> equalizer -> grid gather ->
+    gain, hard bits from the same launch. equalizer "training_symbol" (identity until
+    estimate_channel), "pilot_interp", or None for the bare Rust block.
+
+    One stated divergence: the reference's Python demodulate reads only the first symbol of
+    its input (src/python/ofdm.rs:607-630); this one reads every whole symbol. For a
+    one-symbol input the two agree."""
+    _in, _out = np.complex64, np.complex64
+    _host_fn = staticmethod(lambda *a: _L.orion_ofdm_demod_host(*a))
+
+    def __init__(self, cfg: OfdmConfig, equalizer="training_symbol"):
+        if equalizer not in _OFDM_EQ:
+            raise ValueError(f"OfdmDemod: unknown equalizer {equalizer!r} (expected 'training_symbol' or 'pilot_interp')")
+        super().__init__(_L.orion_ofdm_demod_new(cfg._h, _OFDM_EQ[equalizer]), cfg)
+        self.equalizer = equalizer
+        self._start = cfg.cp_len - min(cfg.rx_window_backoff, cfg.cp_len)
+        self._fft = None
+
+    def set_gain(self, g: float):
+        _check(_L.orion_ofdm_set_gain(self._h, float(g)))
+
+    def estimate_channel(self, training_iq):
+        """estimate_channel (src/python/ofdm.rs:563-582): one received training symbol's IQ
+        (cyclic prefix included) -> the held channel estimate; the window is the demodulator's
+        own (the configuration's back-off). A no-op under "pilot_interp"."""
+        if self.equalizer is None:
+            raise ValueError("OfdmDemod.estimate_channel: this demodulator has no equalizer")
+        iq = _ofdm_arr(training_iq, np.complex64, "training_iq")
+        if iq.size < self.samples_per_ofdm_symbol:
+            raise ValueError(f"OfdmDemod.estimate_channel: input too short ({iq.size} < {self.samples_per_ofdm_symbol})")
+        if self._fft is None:
+            self._fft = FftBlock(self.n_fft)
+        freq = self._fft.process(np.ascontiguousarray(iq[self._start: self._start + self.n_fft]))
+        _arg_check(_L.orion_ofdm_estimate_channel(self._h, freq.ctypes.data, freq.size))
+
+    def estimate_channel_freq(self, received_freq):
+        """The same from the training symbol's n_fft received bins."""
+        r = _ofdm_arr(received_freq, np.complex64, "received_freq")
+        if self.equalizer is None:
+            raise ValueError("OfdmDemod.estimate_channel: this demodulator has no equalizer")
+        _arg_check(_L.orion_ofdm_estimate_channel(self._h, r.ctypes.data, r.size))
+
+    def demodulate_soft(self, iq):
+        """(soft symbols, hard bits) of every whole symbol of iq."""
+        if _is_torch(iq):
+            iq = _torch_1d(iq, "complex64", "iq")
+            if iq.numel() < self.samples_per_ofdm_symbol:
+                raise ValueError(f"OfdmDemod.demodulate: input too short ({iq.numel()} < {self.samples_per_ofdm_symbol})")
+            k = iq.numel() // self.samples_per_ofdm_symbol
+            soft, bits, _ = ofdm_demodulate_batch(self, iq[: k * self.samples_per_ofdm_symbol].reshape(1, -1))
+            return soft.reshape(-1), bits.reshape(-1)
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        if iq.size < self.samples_per_ofdm_symbol:
+            raise ValueError(f"OfdmDemod.demodulate: input too short ({iq.size} < {self.samples_per_ofdm_symbol})")
+        k = iq.size // self.samples_per_ofdm_symbol
+        soft, bits, _ = ofdm_demodulate_batch(self, iq[: k * self.samples_per_ofdm_symbol].reshape(1, -1))
+        return soft.reshape(-1), bits.reshape(-1)
+
+    def demodulate(self, iq):
+        return self.demodulate_soft(iq)[1]
+
+    def process(self, iq) -> np.ndarray:
+        """The Block contract: numpy IQ -> the soft symbols of every whole symbol."""
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        out = np.zeros(iq.size // self.samples_per_ofdm_symbol * self.num_data_carriers, np.complex64)
+        self._process(iq, out)
+        return out
+
+    def process_host(self, iq) -> np.ndarray:
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        out = np.zeros(iq.size // self.samples_per_ofdm_symbol * self.num_data_carriers, np.complex64)
+        self.process_host_into(iq, out)
+        return out
+
+
+def ofdm_modulate_batch(mod: OfdmMod, bits, stream=None):
+    """n_channels x n_symbols symbols in one launch: uint8 (n_channels, n_symbols *
+    bits_per_ofdm_symbol) -> complex64 (n_channels, n_symbols * samples_per_ofdm_symbol). A
+    numpy array costs one upload and one download; a torch CUDA tensor stays resident (queued
+    on torch's current stream or on stream). With rf_hz != 0 every channel continues the
+    modulator's rotator from the same phase."""
+    import torch
+
+    if not _is_torch(bits):
+        if not isinstance(bits, np.ndarray) or bits.dtype != np.uint8 or bits.ndim != 2:
+            raise ValueError("bits: expected a 2-D uint8 array")
+        return ofdm_modulate_batch(mod, torch.from_numpy(np.ascontiguousarray(bits)).cuda(), stream).cpu().numpy()
+    if not bits.is_cuda or not bits.is_contiguous() or bits.dtype != torch.uint8 or bits.dim() != 2:
+        raise ValueError("bits: expected a contiguous 2-D uint8 CUDA tensor")
+    nch, nb = int(bits.shape[0]), int(bits.shape[1])
+    if nb % mod.bits_per_ofdm_symbol:
+        raise ValueError(f"bits: {nb} per channel is not a whole number of symbols ({mod.bits_per_ofdm_symbol} bits each)")
+    nsym = nb // mod.bits_per_ofdm_symbol
+    out = torch.empty((nch, nsym * mod.samples_per_ofdm_symbol), dtype=torch.complex64, device=bits.device)
+    _arg_check(_L.orion_ofdm_mod_device(mod._h, bits.data_ptr(), nch, nsym, out.data_ptr(),
+                                        SyncEngine._stream(bits, stream)))
+    return out
+
+
+def ofdm_demodulate_batch(demod: OfdmDemod, iq, bits=True, llr=False, stream=None):
+    """n_channels x n_symbols symbols in one launch: complex64 (n_channels, n_symbols *
+    samples_per_ofdm_symbol) -> (soft complex64 (n_channels, n_symbols * data carriers), bits
+    uint8 or None, llr float32 or None), the last two (n_channels, n_symbols *
+    bits_per_ofdm_symbol). numpy in, numpy out (one upload); torch CUDA tensors stay resident."""
+    import torch
+
+    if not _is_torch(iq):
+        if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != 2:
+            raise ValueError("iq: expected a 2-D complex64 array")
+        r = ofdm_demodulate_batch(demod, torch.from_numpy(np.ascontiguousarray(iq)).cuda(), bits, llr, stream)
+        return tuple(None if t is None else t.cpu().numpy() for t in r)
+    if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+        raise ValueError("iq: expected a contiguous 2-D complex64 CUDA tensor")
+    nch, n = int(iq.shape[0]), int(iq.shape[1])
+    if n % demod.samples_per_ofdm_symbol:
+        raise ValueError(f"iq: {n} per channel is not a whole number of symbols ({demod.samples_per_ofdm_symbol} samples each)")
+    nsym = n // demod.samples_per_ofdm_symbol
+    soft = torch.empty((nch, nsym * demod.num_data_carriers), dtype=torch.complex64, device=iq.device)
+    b = torch.empty((nch, nsym * demod.bits_per_ofdm_symbol), dtype=torch.uint8, device=iq.device) if bits else None
+    l = torch.empty((nch, nsym * demod.bits_per_ofdm_symbol), dtype=torch.float32, device=iq.device) if llr else None
+    _arg_check(_L.orion_ofdm_demod_device(demod._h, iq.data_ptr(), nch, nsym, soft.data_ptr(),
+                                          b.data_ptr() if bits else None, l.data_ptr() if llr else None,
+                                          SyncEngine._stream(iq, stream)))
+    return soft, b, l
+
+
+class OfdmRxFrame:
+    """OfdmRxFrame (demodulate/ofdm.rs:173-226; src/python/ofdm.rs:637-673): the symbol layer
+    fills bits, num_symbols and evm_db; every other field is None."""
+
+    def __init__(self, bits, num_symbols, evm_db):
+        self.bits, self.num_symbols, self.evm_db = bits, num_symbols, evm_db
+        self.cfo_hz = self.timing_offset_samples = self.channel_mse = None
+        self.sync_score = self.channel_estimate = self.inner_fec_ok = self.outer_fec_ok = None
+        self.channel_ber = self.inner_ber = None
+
+
+def build_ofdm_rx_frame(cfg: OfdmConfig, soft_symbols, bits) -> OfdmRxFrame:
+    """build_ofdm_rx_frame (demodulate/ofdm.rs:238-293): EVM of the soft symbols against the
+    ideal points of the hard bits, f64 sums (host only)."""
+    soft = _ofdm_arr(soft_symbols, np.complex64, "soft_symbols")
+    bits = _ofdm_arr(bits, np.uint8, "bits")
+    nd = cfg.num_data_carriers
+    nsym = soft.size // nd if nd else 0
+    evm, valid = C.c_float(0.0), C.c_int(0)
+    _check(_L.orion_ofdm_evm_db_host(_ofdm_order(cfg.constellation), soft.ctypes.data, soft.size, bits.ctypes.data,
+                                     bits.size, nsym, C.byref(evm), C.byref(valid)))
+    return OfdmRxFrame(bits.copy(), nsym, float(evm.value) if valid.value else None)
