@@ -42,6 +42,40 @@ template <> struct RecSel<RecK::ONEPOLE> {
   __device__ static T make(const ScanCoef& c) { return T{c.a}; }
 };
 
+// A lane run's zero-state end state for the scan combine (k_scan_agg, k_scan_apply), in f64.
+// The LP / one-pole states are the reference's f32 update. The DC blocker's y is run in
+// f64: from a zero state its first step sees x - 0, so on an input with an offset the
+// lane's y is of the offset's size while the true y (entering state included) is small,
+// and the combine cancels the two. An f32 run leaves its rounding (~u |offset|, the same
+// in every lane of a constant input) behind that cancellation, summed over 1 / (1 - r^C)
+// lanes: a DC leak of ~1e-4 of the offset at r = 0.9999 (tests/test_gpu_scan_exact.py,
+// the step input). The f64 run's is 1e-16 of it. The outputs are still the f32 re-run.
+template <class R>
+__device__ __forceinline__ void zero_state_step(const R& rec, float (&s)[R::S], double (&dc)[2], float x) {
+  (void)dc;
+  (void)rec.step(s, x);
+}
+__device__ __forceinline__ void zero_state_step(const RecDC& rec, float (&s)[2], double (&dc)[2], float x) {
+  (void)s;
+  dc[1] = (static_cast<double>(x) - dc[0]) + static_cast<double>(rec.r) * dc[1];
+  dc[0] = static_cast<double>(x);
+}
+__device__ __forceinline__ void zero_state_step(const RecLpDc& rec, float (&s)[6], double (&dc)[2], float x) {
+  const float y0 = rec.bq.step(s[0], s[1], x);
+  const float y1 = rec.bq.step(s[2], s[3], y0);
+  dc[1] = (static_cast<double>(y1) - dc[0]) + static_cast<double>(rec.r) * dc[1];
+  dc[0] = static_cast<double>(y1);
+}
+template <class R>
+__device__ __forceinline__ void zero_state_end(const float (&s)[R::S], const double (&dc)[2], double (&q)[R::S]) {
+#pragma unroll
+  for (int i = 0; i < R::S; ++i) q[i] = s[i];
+  if constexpr (std::is_same_v<R, RecDC> || std::is_same_v<R, RecLpDc>) {
+    q[R::S - 2] = dc[0];
+    q[R::S - 1] = dc[1];
+  }
+}
+
 // Translated (fm.rs:48-49) or raw complex sample i of channel ch; i may be the
 // sample just before this workgroup. Sample i's phasor: oscillator output k0 + i (R:
 // the cursor of the workgroup's run from sample base).
@@ -202,16 +236,16 @@ __global__ __launch_bounds__(NT) void k_scan_agg(const ScanArgs a) {
   stage<PR>(a, ch, base, cnt, sb);
   __syncthreads();
   float s[S];
+  double dc[2] = {0.0, 0.0};
 #pragma unroll
   for (int i = 0; i < S; ++i) s[i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < C; ++i) {
     const int e = t * C + i;
-    if (e < cnt) (void)rec.step(s, sb[pos(e)]);
+    if (e < cnt) zero_state_step(rec, s, dc, sb[pos(e)]);
   }
   double q[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) q[i] = s[i];
+  zero_state_end<R>(s, dc, q);
   wave_scan_inclusive<S>(q, a.mats + ScanMatsLayout::kPwc * S * S, lane);
   if (lane == 63)
 #pragma unroll
@@ -353,14 +387,14 @@ __global__ __launch_bounds__(NT) void k_scan_apply(const ScanArgs a) {
 #pragma unroll
   for (int i = 0; i < C; ++i) xs[i] = sb[pos(t * C + i)];
   float s0[S];
+  double dc[2] = {0.0, 0.0};
 #pragma unroll
   for (int i = 0; i < S; ++i) s0[i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < C; ++i)
-    if (t * C + i < cnt) (void)rec.step(s0, xs[i]);
+    if (t * C + i < cnt) zero_state_step(rec, s0, dc, xs[i]);
   double q[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) q[i] = s0[i];
+  zero_state_end<R>(s0, dc, q);
   wave_scan_inclusive<S>(q, a.mats + ScanMatsLayout::kPwc * S * S, lane);
   if (lane == 63)
 #pragma unroll

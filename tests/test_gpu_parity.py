@@ -56,33 +56,22 @@ def floor_tol(base, fn, x):
 
 
 def ssb_truth(oracle, x, fs=48e3, bfo=1500.0, bw=2800.0):
-    """SsbProductDemod (ssb.rs:28-71) in f64 arithmetic: the reference's own BFO phasors
-    (its f32 recurrence, from the oracle), the product I p.re + Q p.im, then the
-    LpDcCascade (iir.rs:151-165: two TDF-II biquads and the DC blocker) with the
-    reference's f32 coefficients, all in f64 (scipy lfilter). Test infrastructure: the
-    yardstick for how far the reference's own f32 arithmetic is from exact."""
-    import scipy.signal as sg
+    """SsbProductDemod (ssb.rs:28-71) in f64 arithmetic (tests/iir_ref.py ssb_truth: the
+    reference's own BFO phasors, the product and the LpDcCascade with the reference's f32
+    coefficients, all in f64). Test infrastructure: the yardstick for how far the
+    reference's own f32 arithmetic is from exact."""
+    import iir_ref
 
-    x = np.asarray(x, np.complex64)
-    p = oracle.rotator(np.ones(len(x), np.complex64), bfo, fs).astype(np.complex128)
-    y = x.real.astype(np.float64) * p.real + x.imag.astype(np.float64) * p.imag
-    b0, b1, b2, a1, a2, r = (float(v) for v in oracle.lpdc_coeffs(fs, np.float32(np.float32(bw) * np.float32(0.9)), 2.0))
-    for _ in range(2):
-        y = sg.lfilter([b0, b1, b2], [1.0, a1, a2], y)
-    return sg.lfilter([1.0, -1.0], [1.0, -r], y)
+    return iir_ref.ssb_truth(oracle, x, fs, bfo, bw)
 
 
 def lpdc_tol(oracle, x, fs, lp_fc, dc_cut, sqrt_map, got):
     """LpDcCascade tolerance (iir.rs:151-165), as ssb_tol: max(1e-6, 2 x the 1-ulp floor,
     5 x the reference's own distance from the same cascade in f64 with its f32
     coefficients). Prints the GPU's own distance from f64 beside the reference's."""
-    import scipy.signal as sg
+    import iir_ref
 
-    b0, b1, b2, a1, a2, r = (float(v) for v in oracle.lpdc_coeffs(fs, np.float32(lp_fc), dc_cut))
-    y = np.asarray(x, np.float64)
-    for _ in range(2):
-        y = sg.lfilter([b0, b1, b2], [1.0, a1, a2], y)
-    truth = sg.lfilter([1.0, -1.0], [1.0, -r], np.sqrt(y) if sqrt_map else y)
+    truth = iir_ref.lpdc64(x, oracle.lpdc_coeffs(fs, np.float32(lp_fc), dc_cut), "sqrt" if sqrt_map else None)
     ref = oracle.lp_dc_cascade(x, fs, lp_fc, dc_cut, sqrt_map)
     own = nrmse(ref, truth)
     f = ulp_floor(lambda v: oracle.lp_dc_cascade(v, fs, lp_fc, dc_cut, sqrt_map), x)
