@@ -316,7 +316,10 @@ const char* orion_block_name(const orion_block* b);
                                    0 .. 2^28 (default 2^20; 0 = the closed-form ideal phasor of the f32 step).
                                    The oscillator state carries on across the change. */
 int orion_block_configure(orion_block* b, int option, long long value);
-/* Designed coefficients, for parity tests: which = 0 primary taps, 1 audio taps. */
+/* Designed coefficients, for parity tests: which = 0 primary taps, 1 audio taps.
+ * AgcRms, AgcRmsIq, CwKeyedMod: which = 2 is a diagnostic of the last device call (waits for
+ * the device): {its chunks, how many of them entered with an envelope that was not their
+ * predecessor's recorded exit and were re-walked}. */
 int orion_block_taps(const orion_block* b, int which, float* out, size_t cap, size_t* n);
 
 /* ---- designs (host only; bit-exact with the reference constructors) ----- */

@@ -82,6 +82,7 @@ def lib():
         "o_run_decim_channels": (_sz, [_f, _sz, _f, _f, _sz, _c64p, _sz, _c64p, _sz]),
         "o_add_awgn": (None, [_c64p, _sz, _f, C.c_uint64]),
         "o_run_agc": (_f, [C.c_int, _f, _f, _f, _f, C.c_void_p, C.c_void_p, _sz, _sz]),
+        "o_run_agc_calls": (_f, [C.c_int, _f, _f, _f, _f, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -228,11 +229,18 @@ def dc_blocker(x, fs, cut_hz, chunk=0):
     return y
 
 
-def agc(x, fs, attack_ms, release_ms, target_rms, chunk=0):
-    """dsp/agc.rs AgcRms (real input) / AgcRmsIq (complex input). Returns (out, end env)."""
+def agc(x, fs, attack_ms, release_ms, target_rms, chunk=0, calls=None):
+    """dsp/agc.rs AgcRms (real input) / AgcRmsIq (complex input). Returns (out, end env).
+    chunk: the stream in calls of that many samples; calls: in calls of these lengths."""
     iq = np.iscomplexobj(x)
     x = _c64(x) if iq else _f32(x)
     y = np.empty_like(x)
+    if calls is not None:
+        cuts = np.ascontiguousarray(calls, np.uintp)
+        assert int(cuts.sum()) == len(x) and not chunk
+        env = lib().o_run_agc_calls(int(iq), fs, attack_ms, release_ms, target_rms,
+                                    x.ctypes.data, y.ctypes.data, cuts.ctypes.data, len(cuts))
+        return y, env
     env = lib().o_run_agc(int(iq), fs, attack_ms, release_ms, target_rms,
                           x.ctypes.data, y.ctypes.data, len(x), chunk)
     return y, env

@@ -20,7 +20,8 @@
 #define O_FRAC_PI_2 1.57079632679489661923f
 #define O_FRAC_PI_4 0.78539816339744830962f
 
-static inline float o_maxf(float a, float b) { return a > b ? a : (b > a ? b : a); }
+/* f32::max: the other operand when one is NaN */
+static inline float o_maxf(float a, float b) { return a > b ? a : (b > a ? b : (a != a ? b : a)); }
 static inline float o_clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 /* util.rs:305-322 — 5th-order "minimax" atan2; restated op for op. */
@@ -950,5 +951,14 @@ float o_run_agc(int iq, float fs, float attack_ms, float release_ms, float targe
     o_agc a; o_agc_init(&a, fs, attack_ms, release_ms, target_rms);
     const size_t w = iq ? 2 : 1;
     for (size_t i = 0; i < n;) { size_t c = o_step(chunk, n - i); o_agc_process(&a, iq, in + w * i, out + w * i, c); i += c; }
+    return a.env;
+}
+/* The same, in ncalls calls of calls[k] samples each (the seed rule applies per call, agc.rs:57-60). */
+float o_run_agc_calls(int iq, float fs, float attack_ms, float release_ms, float target_rms,
+                      const float *in, float *out, const size_t *calls, size_t ncalls) {
+    o_agc a; o_agc_init(&a, fs, attack_ms, release_ms, target_rms);
+    const size_t w = iq ? 2 : 1;
+    size_t i = 0;
+    for (size_t k = 0; k < ncalls; k++) { o_agc_process(&a, iq, in + w * i, out + w * i, calls[k]); i += calls[k]; }
     return a.env;
 }

@@ -211,6 +211,9 @@ size_t o_run_decim_channels(float fs, size_t m, float cutoff_hz, float trans_hz,
 /* dsp/agc.rs AgcRms (iq = 0, f32) / AgcRmsIq (iq = 1, cf32 interleaved); returns the end env. */
 float o_run_agc(int iq, float fs, float attack_ms, float release_ms, float target_rms,
                 const float *in, float *out, size_t n, size_t chunk);
+/* ... in ncalls calls of calls[k] samples each. */
+float o_run_agc_calls(int iq, float fs, float attack_ms, float release_ms, float target_rms,
+                      const float *in, float *out, const size_t *calls, size_t ncalls);
 
 #ifdef __cplusplus
 }

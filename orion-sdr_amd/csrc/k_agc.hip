@@ -212,6 +212,9 @@ __device__ __forceinline__ void agc_wave_walk_n(const typename Pol::In* __restri
                                                 float (&env)[NT], const Pol& P, float* __restrict__ sm) {
   using T = typename Pol::In;
   using A = typename Pol::Aux;
+  // an empty range (chunk 0's warm-up in k_agc_wave, every warm-up when W == 0): the
+  // clamped prefetch below would read x[e - 1], one element before the buffer when e == 0
+  if (s >= e) return;
   const int lane = threadIdx.x & 63;
   const bool uni = P.att == P.rel && P.oma == P.omr;  // kernel-argument uniform
   // inputs (and output phasors) of the next kAhead blocks in flight: a block's chain
@@ -532,6 +535,7 @@ class EnvelopeRunner {
   void run(const void* in, void* out, long long n, const Pol& P, hipStream_t s) {
     const long long L = chunk_len(n);
     const long long chunks = (n + L - 1) / L;
+    last_chunks_ = chunks;
     float* e = env_.as<float>();
     float* ein = e + cur_;
     float* eout = e + (cur_ ^ 1);
@@ -573,11 +577,26 @@ class EnvelopeRunner {
     env_.zero();
     cur_ = 0;
   }
+  // Diagnostics (taps(2) of the blocks; waits for the device): the chunks of the last call
+  // and how many of them pass 2 flagged, i.e. entered with an envelope that was not their
+  // predecessor's recorded exit (undetermined ones and their successors included).
+  std::vector<float> last_call() const {
+    long long flagged = 0;
+    if (last_chunks_ > 1) {
+      std::vector<unsigned char> bad(static_cast<size_t>(last_chunks_));
+      const float* ent = reinterpret_cast<const float*>(chunk_state_.as<long long>() + 2);
+      ORION_HIP(hipDeviceSynchronize());
+      ORION_HIP(hipMemcpy(bad.data(), ent + 2 * last_chunks_, bad.size(), hipMemcpyDeviceToHost));
+      for (long long c = 1; c < last_chunks_; ++c) flagged += bad[c];
+    }
+    return {static_cast<float>(last_chunks_), static_cast<float>(flagged)};
+  }
 
  private:
   // Up to this many chunks (four waves per SIMD), a wave per chunk (k_agc_wave).
   static constexpr long long kWaveChunks = 4096;
   long long warm_ = 0;
+  long long last_chunks_ = 0;
   DevBuf env_;          // two floats: the carried envelope, ping-ponged per call
   DevBuf chunk_state_;  // first disagreeing chunk, then ent[chunks], ext[chunks]
   int cur_ = 0;
@@ -619,6 +638,7 @@ class AgcBlock final : public Block {
   void reset() override { runner_.reset(); }
   std::vector<float> taps(int which) const override {
     if (which == 1) return {static_cast<float>(runner_.chunk_len(1LL << 24))};
+    if (which == 2) return runner_.last_call();
     return {k_.att, k_.rel, k_.tgt, static_cast<float>(runner_.warm())};
   }
 
@@ -661,7 +681,10 @@ class CwModBlock final : public Block {
     osc_.set_budget(static_cast<uint64_t>(value));
     return 0;
   }
-  std::vector<float> taps(int) const override { return {rise_, fall_, osc_.osc().w_re, osc_.osc().w_im}; }
+  std::vector<float> taps(int which) const override {
+    if (which == 2) return runner_.last_call();
+    return {rise_, fall_, osc_.osc().w_re, osc_.osc().w_im};
+  }
 
  private:
   // cw.rs:27-30: tau = (max(ms, 0.1) * 1e-3) * fs; alpha = exp(-1 / tau)

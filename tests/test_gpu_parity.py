@@ -1530,15 +1530,21 @@ def test_agc_constant_envelope(gpu_lib, oracle, iq, cfg):
 
 
 def test_agc_edges(gpu_lib, oracle):
-    """Empty input, one sample, silence (seed 1e-12, gain clamps at max_gain), reset."""
+    """Empty input, one sample, silence (seed 1e-12, gain clamps at max_gain), reset: bit
+    for bit. Silence alone puts out g * 0 = 0 whatever the envelope is, so two inputs make
+    the output depend on it: a level after silence, and a burst of 200 samples between two
+    silences (the envelope decayed from the 1e-12 seed when it arrives)."""
     blk = gpu_lib.AgcRms(48e3, 0.2, 5.0, 0.2)
     assert blk.process(np.zeros(0, np.float32)).shape == (0,)
+    burst = np.zeros(50_200, np.float32)
+    burst[30_000:30_200] = 0.3 * np.cos(0.05 * np.arange(200))
     for x in (np.array([0.5], np.float32), np.zeros(50_000, np.float32),
-              np.concatenate([np.zeros(30_000), 0.3 * np.ones(70_000)]).astype(np.float32)):
+              np.concatenate([np.zeros(30_000), 0.3 * np.ones(70_000)]).astype(np.float32), burst):
         blk.reset()
         got = blk.process(x)
         ref, _ = oracle.agc(x, 48e3, 0.2, 5.0, 0.2)
-        assert np.allclose(got, ref, rtol=1e-6, atol=1e-7)
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    assert np.count_nonzero(ref) > 190, "the burst's output must not be zero"
 
 
 def test_process_device_overlap_rejected(gpu_lib):
