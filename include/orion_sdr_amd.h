@@ -948,6 +948,88 @@ int orion_ofdm_equalize_host(orion_ofdm* h, const void* in, size_t n, void* out,
 int orion_ofdm_set_pilot_bins_host(orion_ofdm* h, const uint32_t* pilot_bins, const void* pilot_val, size_t n_pilots,
                                    const uint32_t* data_bins, size_t n_data);
 
+/* ---- the inner code: punctured convolutional code, soft Viterbi, block interleaver
+ * (src/fec/conv.rs, src/fec/interleaver.rs:53-120) --------------------------------------
+ * A rate 1/2 mother code, terminated by K - 1 zero tail bits and punctured to rate 2/3, 3/4,
+ * 5/6 or 7/8 (matrices of conv.rs:112-120; step t uses column t % period). Bits are uint8,
+ * one per byte, 0 or 1 (only bit 0 of an input byte is read). LLRs are f32 in punctured
+ * order, positive meaning bit 0: what orion_ofdm_demod_device writes as llr.
+ *
+ * A batched call works on nstreams streams, one frame each; all streams of a call share code,
+ * rate, info_bits and interleaver. The interleaver of the frame chain is given as rows, cols
+ * (0, 0: none): the encoder's output goes through interleave_bits (modulate/ofdm_frame.rs:
+ * row-in, column-out blocks of rows * cols, the last one zero-padded, so a whole number of
+ * blocks: orion_fec_encoded_len), the decoder's input through deinterleave_llrs
+ * (demodulate/ofdm_frame.rs: full blocks are permuted back; a short last chunk of the n_llr
+ * values is NOT permuted, it passes through as it is).
+ *
+ * Layouts: llr [nstreams][n_llr] f32, bits [nstreams][info_bits] u8, coded
+ * [nstreams][orion_fec_encoded_len] u8. The decoder reads 0.0 where the puncturing deleted a
+ * bit and at every index at or past n_llr or the coded length (n_llr may be shorter or longer
+ * than the coded length).
+ *
+ * Limits: 1 <= info_bits <= 2^24, nstreams <= 2^24, n_llr <= 2^31 - 1, rows * cols <= 2^24,
+ * nstreams * orion_fec_encoded_len <= 2^38. Errors: ORION_E_NULL for a null pointer,
+ * ORION_E_ARG for an unknown code or rate, info_bits == 0, a count above its limit, one of
+ * rows, cols zero and the other not, or a workspace that is too small or not 8-byte aligned
+ * (nothing is launched). nstreams == 0 does nothing. The functions that return a size return 0
+ * for such arguments.
+ *
+ * Only orion_fec_viterbi, orion_fec_viterbi_device, orion_fec_conv_encode_batch and
+ * orion_fec_conv_encode_batch_device touch a device. */
+#define ORION_FEC_K5 0     /* K = 5, G0 = 25, G1 = 23 octal: orion_conv_encode's code */
+#define ORION_FEC_DVB_K7 1 /* K = 7, G0 = 171, G1 = 133 octal (ETSI EN 300 744 4.3.3) */
+#define ORION_FEC_RATE_1_2 0
+#define ORION_FEC_RATE_2_3 1
+#define ORION_FEC_RATE_3_4 2
+#define ORION_FEC_RATE_5_6 3
+#define ORION_FEC_RATE_7_8 4
+/* punctured_coded_len_with, conv.rs:274-288; and that length after interleave_bits. */
+size_t orion_fec_punctured_coded_len(int code, size_t info_bits, int rate);
+size_t orion_fec_encoded_len(int code, size_t info_bits, int rate, size_t rows, size_t cols);
+/* conv_encode_punctured_with, conv.rs:234-263, host only: info [info_bits] -> coded
+ * [orion_fec_punctured_coded_len] (no interleaver). */
+int orion_fec_conv_encode(int code, int rate, const uint8_t* info, size_t info_bits, uint8_t* coded);
+/* The scalar decoder the kernel is held to, one stream, host only: viterbi_decode_soft_with
+ * (conv.rs:304-398) of deinterleave_llrs(llr [n_llr]) -> bits [info_bits]. The start metric
+ * is f32::MIN / 2 with state 0 at 0; a predecessor at or below it is skipped; a survivor is
+ * replaced on strict > only, states visited ascending; the traceback starts at state 0. */
+int orion_fec_viterbi_host(int code, int rate, const float* llr, size_t n_llr, size_t info_bits, size_t rows,
+                           size_t cols, uint8_t* bits);
+/* The same decode of nstreams streams in one launch: one lane per trellis state (K = 7: one
+ * stream per wave; K = 5: sixteen lanes per stream, four streams per wave), depuncturing and
+ * deinterleaving fused into the LLR fetch. The bits are those of orion_fec_viterbi_host for
+ * every input, ties, all-zero input, short input and metrics that overflow included. NaN
+ * input is outside the contract; it neither faults nor hangs. Host slices (uploaded, one
+ * launch, downloaded; synchronous) or device buffers on a stream; the device call needs work,
+ * device memory of at least orion_fec_viterbi_work_bytes(code, nstreams, info_bits) bytes,
+ * 8-byte aligned (K = 5: 4 bytes per stream, rounded up to 4 streams, and trellis step;
+ * K = 7: 16 bytes per stream and step; info_bits + K - 1 steps), which it may overwrite wholly. */
+int orion_fec_viterbi(int code, int rate, const float* llr, size_t nstreams, size_t n_llr, size_t info_bits,
+                      size_t rows, size_t cols, uint8_t* bits);
+int orion_fec_viterbi_device(int code, int rate, const float* llr, size_t nstreams, size_t n_llr, size_t info_bits,
+                             size_t rows, size_t cols, uint8_t* bits, void* work, size_t work_bytes, void* stream);
+size_t orion_fec_viterbi_work_bytes(int code, size_t nstreams, size_t info_bits);
+/* Encode, puncture and interleave nstreams streams in one launch, one thread per output bit:
+ * info [nstreams][info_bits] -> coded [nstreams][orion_fec_encoded_len]; the bytes are those
+ * of orion_fec_conv_encode followed by orion_fec_interleave_bits. Host slices (synchronous)
+ * or device buffers on a stream. */
+int orion_fec_conv_encode_batch(int code, int rate, const uint8_t* info, size_t nstreams, size_t info_bits,
+                                size_t rows, size_t cols, uint8_t* coded);
+int orion_fec_conv_encode_batch_device(int code, int rate, const uint8_t* info, size_t nstreams, size_t info_bits,
+                                       size_t rows, size_t cols, uint8_t* coded, void* stream);
+/* BlockInterleaver, interleaver.rs:53-120, host only, rows and cols nonzero. One block of
+ * rows * cols elements: interleave out[c rows + r] = in[r cols + c], deinterleave its inverse. */
+int orion_fec_interleave_u8(size_t rows, size_t cols, const uint8_t* in, uint8_t* out);
+int orion_fec_interleave_f32(size_t rows, size_t cols, const float* in, float* out);
+int orion_fec_deinterleave_u8(size_t rows, size_t cols, const uint8_t* in, uint8_t* out);
+int orion_fec_deinterleave_f32(size_t rows, size_t cols, const float* in, float* out);
+/* The chain drivers, host only: interleave_bits, bits [n] -> out [orion_fec_interleaved_len
+ * (rows, cols, n)], n rounded up to whole blocks; deinterleave_llrs, llr [n] -> out [n]. */
+size_t orion_fec_interleaved_len(size_t rows, size_t cols, size_t n);
+int orion_fec_interleave_bits(size_t rows, size_t cols, const uint8_t* bits, size_t n, uint8_t* out);
+int orion_fec_deinterleave_llrs(size_t rows, size_t cols, const float* llr, size_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

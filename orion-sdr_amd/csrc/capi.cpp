@@ -9,6 +9,8 @@
 #include <vector>
 
 #include "blocks.hpp"
+#include "fec.hpp"
+#include "fec_blocks.hpp"
 #include "ldpc.hpp"
 #include "ofdm.hpp"
 #include "ofdm_blocks.hpp"
@@ -87,6 +89,9 @@ static_assert(sizeof(orion_candidate) == sizeof(orion::SyncCandidate) && sizeof(
 static_assert(sizeof(orion_ldpc_result) == sizeof(orion::ldpc::Result) && sizeof(orion_ldpc_result) == 16 &&
                   sizeof(orion_decode_pick) == sizeof(orion::DecodePick) && sizeof(orion_decode_pick) == 16,
               "orion_ldpc_result / orion_decode_pick are the kernels' records");
+static_assert(ORION_FEC_K5 == orion::fec::kK5 && ORION_FEC_DVB_K7 == orion::fec::kDvbK7 &&
+                  ORION_FEC_RATE_1_2 == orion::fec::kR1_2 && ORION_FEC_RATE_7_8 == orion::fec::kR7_8,
+              "the header's constants are fec.hpp's");
 static_assert(ORION_LDPC_N == orion::ldpc::kN && ORION_LDPC_RULE_SUM_PRODUCT == orion::ldpc::kRuleSumProduct &&
                   ORION_LDPC_DECODED == orion::ldpc::kDecoded && ORION_COSTAS_FT4 == orion::ldpc::kFt4,
               "the header's constants are ldpc.hpp's");
@@ -122,6 +127,20 @@ orion_block* make(F&& f) {
     g_err = e.what();
     return nullptr;
   }
+}
+
+// one block through a BlockInterleaver (orion_fec_interleave_* / orion_fec_deinterleave_*)
+template <class T>
+int fec_block(size_t rows, size_t cols, const T* in, T* out, bool inverse) {
+  if (!in || !out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::fec::BlockInterleaver bi(rows, cols);
+    if (inverse)
+      bi.deinterleave(in, out);
+    else
+      bi.interleave(in, out);
+    return ORION_OK;
+  });
 }
 }  // namespace
 
@@ -1798,6 +1817,129 @@ int orion_ofdm_set_pilot_bins_host(orion_ofdm* h, const uint32_t* pilot_bins, co
   if ((n_pilots && (!pilot_bins || !pilot_val)) || (n_data && !data_bins)) return fail(ORION_E_NULL, "null buffer");
   return guarded([&] {
     h->impl.set_pilot_bins(pilot_bins, static_cast<const float*>(pilot_val), n_pilots, data_bins, n_data);
+    return ORION_OK;
+  });
+}
+
+/* ---- the inner code (fec.hpp, k_fec.hip) ---- */
+size_t orion_fec_punctured_coded_len(int code, size_t info_bits, int rate) {
+  try {
+    return info_bits ? orion::fec::punctured_coded_len(code, info_bits, rate) : 0;
+  } catch (const std::exception& e) {
+    fail(ORION_E_ARG, e.what());
+    return 0;
+  }
+}
+size_t orion_fec_encoded_len(int code, size_t info_bits, int rate, size_t rows, size_t cols) {
+  try {
+    return orion::fec_encoded_len(code, info_bits, rate, rows, cols);
+  } catch (const std::exception& e) {
+    fail(ORION_E_ARG, e.what());
+    return 0;
+  }
+}
+int orion_fec_conv_encode(int code, int rate, const uint8_t* info, size_t info_bits, uint8_t* coded) {
+  if (!info || !coded) return fail(ORION_E_NULL, "null buffer");
+  if (info_bits == 0) return fail(ORION_E_ARG, "fec: info_bits == 0");
+  return guarded([&] {
+    orion::fec::conv_encode_punctured(code, info, info_bits, rate, coded);
+    return ORION_OK;
+  });
+}
+int orion_fec_viterbi_host(int code, int rate, const float* llr, size_t n_llr, size_t info_bits, size_t rows,
+                           size_t cols, uint8_t* bits) {
+  if ((n_llr && !llr) || !bits) return fail(ORION_E_NULL, "null buffer");
+  if (info_bits == 0) return fail(ORION_E_ARG, "fec: info_bits == 0");
+  if ((rows == 0) != (cols == 0)) return fail(ORION_E_ARG, "fec: interleaver rows, cols both zero (none) or both nonzero");
+  if (n_llr > orion::fec::kMaxLlr) return fail(ORION_E_ARG, "fec viterbi: n_llr above 2^31 - 1");
+  return guarded([&] {
+    if (rows) {
+      const std::vector<float> d = orion::fec::BlockInterleaver(rows, cols).deinterleave_llrs(llr, n_llr);
+      orion::fec::viterbi_decode_soft(code, d.data(), n_llr, info_bits, rate, bits);
+    } else {
+      orion::fec::viterbi_decode_soft(code, llr, n_llr, info_bits, rate, bits);
+    }
+    return ORION_OK;
+  });
+}
+int orion_fec_viterbi(int code, int rate, const float* llr, size_t nstreams, size_t n_llr, size_t info_bits,
+                      size_t rows, size_t cols, uint8_t* bits) {
+  if (nstreams && ((n_llr && !llr) || !bits)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::fec_viterbi_host(code, rate, llr, nstreams, n_llr, info_bits, rows, cols, bits);
+    return ORION_OK;
+  });
+}
+int orion_fec_viterbi_device(int code, int rate, const float* llr, size_t nstreams, size_t n_llr, size_t info_bits,
+                             size_t rows, size_t cols, uint8_t* bits, void* work, size_t work_bytes, void* stream) {
+  if (nstreams && ((n_llr && !llr) || !bits || !work)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::fec_viterbi(code, rate, llr, nstreams, n_llr, info_bits, rows, cols, bits, work, work_bytes,
+                       static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_fec_viterbi_work_bytes(int code, size_t nstreams, size_t info_bits) {
+  if (info_bits == 0 || info_bits > orion::fec::kMaxInfoBits || nstreams > orion::fec::kMaxStreams) return 0;
+  try {
+    return orion::fec::viterbi_work_bytes(orion::fec::code_spec(code).reg_bits, nstreams, info_bits);
+  } catch (const std::exception& e) {
+    fail(ORION_E_ARG, e.what());
+    return 0;
+  }
+}
+int orion_fec_conv_encode_batch(int code, int rate, const uint8_t* info, size_t nstreams, size_t info_bits,
+                                size_t rows, size_t cols, uint8_t* coded) {
+  if (nstreams && (!info || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::fec_encode_batch_host(code, rate, info, nstreams, info_bits, rows, cols, coded);
+    return ORION_OK;
+  });
+}
+int orion_fec_conv_encode_batch_device(int code, int rate, const uint8_t* info, size_t nstreams, size_t info_bits,
+                                       size_t rows, size_t cols, uint8_t* coded, void* stream) {
+  if (nstreams && (!info || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::fec_encode_batch(code, rate, info, nstreams, info_bits, rows, cols, coded, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_fec_interleave_u8(size_t rows, size_t cols, const uint8_t* in, uint8_t* out) {
+  return fec_block(rows, cols, in, out, false);
+}
+int orion_fec_interleave_f32(size_t rows, size_t cols, const float* in, float* out) {
+  return fec_block(rows, cols, in, out, false);
+}
+int orion_fec_deinterleave_u8(size_t rows, size_t cols, const uint8_t* in, uint8_t* out) {
+  return fec_block(rows, cols, in, out, true);
+}
+int orion_fec_deinterleave_f32(size_t rows, size_t cols, const float* in, float* out) {
+  return fec_block(rows, cols, in, out, true);
+}
+size_t orion_fec_interleaved_len(size_t rows, size_t cols, size_t n) {
+  try {
+    if (n > (size_t(1) << 40)) throw std::invalid_argument("interleaver: n above 2^40");
+    return orion::fec::BlockInterleaver(rows, cols).interleaved_len(n);
+  } catch (const std::exception& e) {
+    fail(ORION_E_ARG, e.what());
+    return 0;
+  }
+}
+int orion_fec_interleave_bits(size_t rows, size_t cols, const uint8_t* bits, size_t n, uint8_t* out) {
+  if (n && (!bits || !out)) return fail(ORION_E_NULL, "null buffer");
+  if (n > (size_t(1) << 40)) return fail(ORION_E_ARG, "interleaver: n above 2^40");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::fec::BlockInterleaver(rows, cols).interleave_bits(bits, n);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_fec_deinterleave_llrs(size_t rows, size_t cols, const float* llr, size_t n, float* out) {
+  if (n && (!llr || !out)) return fail(ORION_E_NULL, "null buffer");
+  if (n > (size_t(1) << 40)) return fail(ORION_E_ARG, "interleaver: n above 2^40");
+  return guarded([&] {
+    const std::vector<float> v = orion::fec::BlockInterleaver(rows, cols).deinterleave_llrs(llr, n);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(float));
     return ORION_OK;
   });
 }

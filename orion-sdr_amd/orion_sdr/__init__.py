@@ -3081,3 +3081,210 @@ def build_ofdm_rx_frame(cfg: OfdmConfig, soft_symbols, bits) -> OfdmRxFrame:
     _check(_L.orion_ofdm_evm_db_host(_ofdm_order(cfg.constellation), soft.ctypes.data, soft.size, bits.ctypes.data,
                                      bits.size, nsym, C.byref(evm), C.byref(valid)))
     return OfdmRxFrame(bits.copy(), nsym, float(evm.value) if valid.value else None)
+
+
+# ---- the inner code: punctured convolutional code, soft Viterbi, block interleaver (src/fec) ----
+def _fec_sigs():
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    sig = {
+        "orion_fec_punctured_coded_len": (sz, [i, sz, i]), "orion_fec_encoded_len": (sz, [i, sz, i, sz, sz]),
+        "orion_fec_conv_encode": (i, [i, i, vp, sz, vp]),
+        "orion_fec_viterbi_host": (i, [i, i, vp, sz, sz, sz, sz, vp]),
+        "orion_fec_viterbi": (i, [i, i, vp, sz, sz, sz, sz, sz, vp]),
+        "orion_fec_viterbi_device": (i, [i, i, vp, sz, sz, sz, sz, sz, vp, vp, sz, vp]),
+        "orion_fec_viterbi_work_bytes": (sz, [i, sz, sz]),
+        "orion_fec_conv_encode_batch": (i, [i, i, vp, sz, sz, sz, sz, vp]),
+        "orion_fec_conv_encode_batch_device": (i, [i, i, vp, sz, sz, sz, sz, vp, vp]),
+        "orion_fec_interleave_u8": (i, [sz, sz, vp, vp]), "orion_fec_interleave_f32": (i, [sz, sz, vp, vp]),
+        "orion_fec_deinterleave_u8": (i, [sz, sz, vp, vp]), "orion_fec_deinterleave_f32": (i, [sz, sz, vp, vp]),
+        "orion_fec_interleaved_len": (sz, [sz, sz, sz]),
+        "orion_fec_interleave_bits": (i, [sz, sz, vp, sz, vp]),
+        "orion_fec_deinterleave_llrs": (i, [sz, sz, vp, sz, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_fec_sigs()
+
+FEC_CODES = {"k5": 0, "dvb_k7": 1}  # conv.rs:41-50
+FEC_RATES = {"1/2": 0, "2/3": 1, "3/4": 2, "5/6": 3, "7/8": 4}  # conv.rs:99-106
+__all__ += ["FEC_CODES", "FEC_RATES", "punctured_coded_len", "conv_encode_punctured", "viterbi_decode_soft",
+            "BlockInterleaver", "conv_encode_batch", "conv_viterbi_batch"]
+
+
+def _fec_code(code) -> int:
+    if code not in FEC_CODES:
+        raise ValueError(f"code: one of {sorted(FEC_CODES)}")
+    return FEC_CODES[code]
+
+
+def _fec_rate(rate) -> int:
+    if rate not in FEC_RATES:
+        raise ValueError(f"rate: one of {list(FEC_RATES)}")
+    return FEC_RATES[rate]
+
+
+def _fec_il(interleaver):
+    if interleaver is None:
+        return 0, 0
+    if isinstance(interleaver, BlockInterleaver):
+        return interleaver.rows, interleaver.cols
+    rows, cols = interleaver
+    return BlockInterleaver(rows, cols).rows, int(cols)
+
+
+def _fec_info_bits(info_bits) -> int:
+    info_bits = int(info_bits)
+    if info_bits < 1:
+        raise ValueError("info_bits: at least 1")
+    return info_bits
+
+
+def punctured_coded_len(info_bits, rate, code="k5") -> int:
+    """punctured_coded_len_with (conv.rs:274-288): the coded bits of info_bits information
+    bits and the K - 1 tail bits at rate "1/2" .. "7/8" under code "k5" / "dvb_k7"."""
+    c, r, n = _fec_code(code), _fec_rate(rate), _fec_info_bits(info_bits)
+    out = int(_L.orion_fec_punctured_coded_len(c, n, r))
+    if out == 0:
+        raise ValueError(_err())
+    return out
+
+
+def conv_encode_punctured(bits, rate, code="k5") -> np.ndarray:
+    """conv_encode_punctured_with (conv.rs:234-263), host only: uint8 information bits (n,) ->
+    coded bits (punctured_coded_len(n, rate, code),): the zero tail, the mother code's (g0, g1)
+    pairs, the rate's puncturing."""
+    bits = _bits_arg(bits)
+    out = np.zeros(punctured_coded_len(bits.size, rate, code), np.uint8)
+    _arg_check(_L.orion_fec_conv_encode(_fec_code(code), _fec_rate(rate), bits.ctypes.data, bits.size, out.ctypes.data))
+    return out
+
+
+def viterbi_decode_soft(llr, info_bits, rate, code="k5") -> np.ndarray:
+    """viterbi_decode_soft_with (conv.rs:304-398) by the library's scalar decoder (host only;
+    what the kernel is held to): float32 LLRs (n_llr,) in punctured order, positive meaning
+    bit 0 -> uint8 bits (info_bits,). LLRs past n_llr read as 0.0."""
+    if not isinstance(llr, np.ndarray) or llr.dtype != np.float32 or llr.ndim != 1:
+        raise ValueError("llr: expected a 1-D float32 array")
+    llr = np.ascontiguousarray(llr)
+    out = np.zeros(_fec_info_bits(info_bits), np.uint8)
+    _arg_check(_L.orion_fec_viterbi_host(_fec_code(code), _fec_rate(rate), llr.ctypes.data, llr.size, out.size, 0, 0,
+                                         out.ctypes.data))
+    return out
+
+
+class BlockInterleaver:
+    """BlockInterleaver (fec/interleaver.rs:53-120), host only: interleave / deinterleave take
+    one block of rows * cols uint8 or float32 elements (out[c rows + r] = in[r cols + c] and
+    its inverse); interleave_bits and deinterleave_llrs are the frame chain's drivers
+    (modulate/ofdm_frame.rs, demodulate/ofdm_frame.rs): the first zero-pads the last block,
+    the second leaves a short last chunk as it is."""
+
+    def __init__(self, rows, cols):
+        rows, cols = int(rows), int(cols)
+        if rows < 1 or cols < 1:
+            raise ValueError("interleaver dimensions must be nonzero")
+        if rows * cols > 1 << 24:
+            raise ValueError("interleaver: rows * cols above 2^24")
+        self.rows, self.cols = rows, cols
+
+    @property
+    def block_len(self) -> int:
+        return self.rows * self.cols
+
+    def _block(self, x, inverse):
+        if not isinstance(x, np.ndarray) or x.dtype not in (np.uint8, np.float32) or x.ndim != 1:
+            raise ValueError("expected a 1-D uint8 or float32 array")
+        if x.size != self.block_len:
+            raise ValueError(f"expected one full block of {self.block_len} elements")
+        x = np.ascontiguousarray(x)
+        out = np.empty_like(x)
+        name = f"orion_fec_{'de' if inverse else ''}interleave_{'u8' if x.dtype == np.uint8 else 'f32'}"
+        _arg_check(getattr(_L, name)(self.rows, self.cols, x.ctypes.data, out.ctypes.data))
+        return out
+
+    def interleave(self, x) -> np.ndarray:
+        return self._block(x, False)
+
+    def deinterleave(self, x) -> np.ndarray:
+        return self._block(x, True)
+
+    def interleave_bits(self, bits) -> np.ndarray:
+        bits = _bits_arg(bits)
+        out = np.zeros(int(_L.orion_fec_interleaved_len(self.rows, self.cols, bits.size)), np.uint8)
+        _arg_check(_L.orion_fec_interleave_bits(self.rows, self.cols, bits.ctypes.data, bits.size, out.ctypes.data))
+        return out
+
+    def deinterleave_llrs(self, llr) -> np.ndarray:
+        if not isinstance(llr, np.ndarray) or llr.dtype != np.float32 or llr.ndim != 1:
+            raise ValueError("llr: expected a 1-D float32 array")
+        llr = np.ascontiguousarray(llr)
+        out = np.zeros(llr.size, np.float32)
+        _arg_check(_L.orion_fec_deinterleave_llrs(self.rows, self.cols, llr.ctypes.data, llr.size, out.ctypes.data))
+        return out
+
+
+def conv_encode_batch(bits, rate, code="k5", interleaver=None, stream=None):
+    """Encode, puncture and (with interleaver, a BlockInterleaver or (rows, cols)) block
+    interleave a batch of frames on the GPU in one launch: uint8 (nstreams, info_bits) ->
+    uint8 (nstreams, coded length), the coded length rounded up to whole interleaver blocks
+    (zero padding). Row k is interleave_bits(conv_encode_punctured(bits[k])). A numpy array
+    (-> numpy) or a contiguous torch CUDA tensor (-> a torch tensor on its device, queued on
+    torch's current stream or on stream)."""
+    c, r = _fec_code(code), _fec_rate(rate)
+    rows, cols = _fec_il(interleaver)
+    dev = _is_torch(bits)
+    if dev:
+        import torch
+
+        if not bits.is_cuda or not bits.is_contiguous() or bits.dtype != torch.uint8 or bits.dim() != 2:
+            raise ValueError("conv_encode_batch needs a contiguous 2-D uint8 CUDA tensor")
+    elif not isinstance(bits, np.ndarray) or bits.dtype != np.uint8 or bits.ndim != 2:
+        raise ValueError("bits: expected a 2-D uint8 array")
+    ns, n = int(bits.shape[0]), _fec_info_bits(bits.shape[1])
+    out_len = int(_L.orion_fec_encoded_len(c, n, r, rows, cols))
+    if out_len == 0:
+        raise ValueError(_err())
+    if dev:
+        out = torch.empty((ns, out_len), dtype=torch.uint8, device=bits.device)
+        _arg_check(_L.orion_fec_conv_encode_batch_device(c, r, bits.data_ptr(), ns, n, rows, cols, out.data_ptr(),
+                                                         SyncEngine._stream(bits, stream)))
+        return out
+    bits = np.ascontiguousarray(bits)
+    out = np.zeros((ns, out_len), np.uint8)
+    _arg_check(_L.orion_fec_conv_encode_batch(c, r, bits.ctypes.data, ns, n, rows, cols, out.ctypes.data))
+    return out
+
+
+def conv_viterbi_batch(llr, info_bits, rate, code="k5", interleaver=None, stream=None):
+    """Soft Viterbi decode of a batch of frames on the GPU in one launch (one lane per trellis
+    state: "dvb_k7" one frame per wave, "k5" four), the block deinterleaver and the
+    depuncturing fused into the LLR fetch: float32 (nstreams, n_llr), positive meaning bit 0,
+    -> uint8 (nstreams, info_bits). Row k is viterbi_decode_soft(deinterleave_llrs(llr[k]),
+    info_bits, rate, code) bit for bit. A numpy array (-> numpy) or a contiguous torch CUDA
+    tensor, such as the llr of ofdm_demodulate_batch(..., llr=True) (-> a torch tensor on its
+    device, queued on torch's current stream or on stream)."""
+    c, r, n = _fec_code(code), _fec_rate(rate), _fec_info_bits(info_bits)
+    rows, cols = _fec_il(interleaver)
+    if _is_torch(llr):
+        import torch
+
+        if not llr.is_cuda or not llr.is_contiguous() or llr.dtype != torch.float32 or llr.dim() != 2:
+            raise ValueError("conv_viterbi_batch needs a contiguous 2-D float32 CUDA tensor")
+        ns, nl = int(llr.shape[0]), int(llr.shape[1])
+        bits = torch.empty((ns, n), dtype=torch.uint8, device=llr.device)
+        wb = int(_L.orion_fec_viterbi_work_bytes(c, ns, n))
+        work = torch.empty(max(wb // 8, 1), dtype=torch.int64, device=llr.device)
+        _arg_check(_L.orion_fec_viterbi_device(c, r, llr.data_ptr(), ns, nl, n, rows, cols, bits.data_ptr(),
+                                               work.data_ptr(), wb, SyncEngine._stream(llr, stream)))
+        return bits
+    if not isinstance(llr, np.ndarray) or llr.dtype != np.float32 or llr.ndim != 2:
+        raise ValueError("llr: expected a 2-D float32 array")
+    llr = np.ascontiguousarray(llr)
+    ns, nl = llr.shape
+    bits = np.zeros((ns, n), np.uint8)
+    _arg_check(_L.orion_fec_viterbi(c, r, llr.ctypes.data, ns, nl, n, rows, cols, bits.ctypes.data))
+    return bits
