@@ -1030,6 +1030,134 @@ size_t orion_fec_interleaved_len(size_t rows, size_t cols, size_t n);
 int orion_fec_interleave_bits(size_t rows, size_t cols, const uint8_t* bits, size_t n, uint8_t* out);
 int orion_fec_deinterleave_llrs(size_t rows, size_t cols, const float* llr, size_t n, float* out);
 
+/* ---- the outer code: Reed-Solomon over GF(2^8), the Forney byte interleaver, the PN scrambler,
+ * DVB-T energy dispersal and the transport-stream packet layer (src/fec/gf.rs,
+ * reed_solomon.rs, interleaver.rs:122-305, scrambler.rs; src/waveform/dvb_t.rs:30-110,
+ * dvb_t_ts.rs) --------------------------------------------------------------------------------
+ * A code is (n, n_parity): n codeword bytes, k = n - n_parity message bytes, byte 0 the
+ * highest-degree symbol, first consecutive root 0, field polynomial 0x11D; n < 255 is the
+ * shortened code. 1 <= n <= 255 and n_parity < n (the reference's check); t = n_parity / 2,
+ * rounded down. DVB-T's outer code is (204, 16).
+ *
+ * The decoder is the reference's decode_counted step for step: the Chien search runs over all
+ * 255 degrees; a root on a degree that is never transmitted counts as a root and is not
+ * applied; a zero magnitude is not counted; the syndromes of the corrected word decide. Its
+ * status is the number of codeword bytes it changed (parity bytes included), or -1 for an
+ * uncorrectable word, whose message is then the systematic prefix received[:k].
+ *
+ * The Forney interleaver has I = branches and M = depth (DVB-T: 12, 17), both nonzero and
+ * I * I * M <= 2^24; its round-trip delay is D = I (I - 1) M bytes. Frame mode: the payload is
+ * zero-padded to a multiple of I bytes, fed through a fresh interleaver and followed by the
+ * flush, round_up(n, I) + D bytes (orion_rs_forney_frame_len); the deinterleaver returns bytes
+ * D .. total of a fresh deinterleaver's output.
+ *
+ * Only orion_rs_decode_batch / _device, orion_rs_encode_batch / _device and
+ * orion_rs_forney_interleave_batch / _device touch a device; nstreams == 0 does nothing.
+ * Device limits: 1 <= n_parity <= 32, 1 <= ncw <= 2^20, nstreams <= 2^24, nstreams * ncw <=
+ * 2^30, the interleaver's input 1 <= len <= 2^27 bytes and at most 2^38 output elements.
+ * Errors: ORION_E_NULL for a null pointer or handle, ORION_E_ARG for everything else that is
+ * out of range (nothing is launched). The functions that return a size return 0 for such
+ * arguments. */
+typedef struct orion_rs_forney orion_rs_forney;
+typedef struct orion_rs_pn_stream orion_rs_pn_stream;
+typedef struct orion_rs_dispersal orion_rs_dispersal;
+/* Gf256: the tables exp [512] (2^i, the cycle of 255 repeated) and log [256]; mul, div, inv,
+ * pow (n reduced modulo 255; 0^0 = 1) and exp_of (i modulo 255) return the element 0..255, or
+ * ORION_E_ARG for an operand above 255, a division by zero or the inverse of zero. */
+int orion_rs_gf_tables(uint8_t* exp, uint8_t* log);
+int orion_rs_gf_mul(unsigned a, unsigned b);
+int orion_rs_gf_div(unsigned a, unsigned b);
+int orion_rs_gf_inv(unsigned a);
+int orion_rs_gf_pow(unsigned a, size_t n);
+int orion_rs_gf_exp_of(size_t i);
+/* The generator polynomial, low degree first: out [n_parity + 1]. */
+int orion_rs_generator(size_t n, size_t n_parity, uint8_t* out);
+/* Host only, nwords words one after another: msgs [nwords][k] -> cws [nwords][n] (n_parity ==
+ * 0: ORION_E_ARG, the reference's shift register has no cell); words [nwords][n] -> msgs
+ * [nwords][k], status [nwords]. */
+int orion_rs_encode(size_t n, size_t n_parity, const uint8_t* msgs, size_t nwords, uint8_t* cws);
+int orion_rs_decode_counted(size_t n, size_t n_parity, const uint8_t* words, size_t nwords, uint8_t* msgs,
+                            int32_t* status);
+/* ConvInterleaver (inverse == 0) / ConvDeinterleaver (inverse != 0) as streaming blocks: feed
+ * is 1:1 in length (in [n] -> out [n], in == out allowed) and carries the delay lines across
+ * calls; flush feeds D zeros (out [D]); reset clears the lines and the commutator. */
+orion_rs_forney* orion_rs_forney_new(size_t branches, size_t depth, int inverse);
+void orion_rs_forney_free(orion_rs_forney* f);
+int orion_rs_forney_feed(orion_rs_forney* f, const uint8_t* in, size_t n, uint8_t* out);
+int orion_rs_forney_flush(orion_rs_forney* f, uint8_t* out);
+int orion_rs_forney_reset(orion_rs_forney* f);
+size_t orion_rs_forney_delay(size_t branches, size_t depth); /* 0 for bad dimensions, and for I == 1 */
+/* Frame mode, host only: bytes [n] -> out [orion_rs_forney_frame_len(branches, depth, n)];
+ * bytes [total] -> out [total - D] (total <= D: nothing is written). */
+size_t orion_rs_forney_frame_len(size_t branches, size_t depth, size_t n);
+int orion_rs_forney_frame_interleave(size_t branches, size_t depth, const uint8_t* bytes, size_t n, uint8_t* out);
+int orion_rs_forney_frame_deinterleave(size_t branches, size_t depth, const uint8_t* bytes, size_t total,
+                                       uint8_t* out);
+/* PnScrambler: a Fibonacci LFSR of width bits (2..=32) from seed (nonzero; seed and taps fit in
+ * width bits); the scrambling bit is bit 0, the feedback the parity of reg & taps, inserted at
+ * bit width - 1; data bits LSB first. orion_rs_pn_scramble restarts from seed (in place,
+ * self-inverse); a stream carries the register across feeds (in place) until reset. */
+int orion_rs_pn_scramble(uint32_t taps, uint32_t width, uint32_t seed, uint8_t* data, size_t n);
+orion_rs_pn_stream* orion_rs_pn_stream_new(uint32_t taps, uint32_t width, uint32_t seed);
+void orion_rs_pn_stream_free(orion_rs_pn_stream* s);
+int orion_rs_pn_stream_feed(orion_rs_pn_stream* s, uint8_t* data, size_t n);
+int orion_rs_pn_stream_reset(orion_rs_pn_stream* s);
+/* DvbTEnergyDispersal: PRBS 1 + X^14 + X^15 from 100101010000000, data bits MSB first, the
+ * register carried across feeds (in place); advance_byte clocks eight steps without output. */
+orion_rs_dispersal* orion_rs_dispersal_new(void);
+void orion_rs_dispersal_free(orion_rs_dispersal* d);
+int orion_rs_dispersal_feed(orion_rs_dispersal* d, uint8_t* data, size_t n);
+int orion_rs_dispersal_advance_byte(orion_rs_dispersal* d);
+int orion_rs_dispersal_reset(orion_rs_dispersal* d);
+/* The transport-stream layer, host only. ts_energy_disperse: in place over n bytes, a multiple
+ * of 188 (ORION_E_ARG otherwise): the PRBS restarts every eight packets, the first sync byte
+ * of a group is flipped 0x47 <-> 0xB8, the other seven are clocked over, every payload byte
+ * is whitened; self-inverse. ts_dispersal_mask: what that XORs onto a group, out [1504], the
+ * kernels' table. ts_packetize: payload [n] -> out [orion_rs_ts_packetized_len(n)], max(1,
+ * ceil(n / 187)) packets of 0x47 and 187 payload bytes. ts_depacketize: packets [n], n a
+ * nonzero multiple of 188 -> out [n / 188 * 187]. ts_null_packet: out [188] = 47 1F FF 10 and
+ * 0xFF. ts_stuff_null_packets: ts [n], whole packets -> out [max(n / 188, target_packets) *
+ * 188], ts followed by null packets. */
+int orion_rs_ts_energy_disperse(uint8_t* packets, size_t n);
+int orion_rs_ts_dispersal_mask(uint8_t* out);
+size_t orion_rs_ts_packetized_len(size_t n);
+int orion_rs_ts_packetize(const uint8_t* payload, size_t n, uint8_t* out);
+int orion_rs_ts_depacketize(const uint8_t* packets, size_t n, uint8_t* out);
+int orion_rs_ts_null_packet(uint8_t* out);
+int orion_rs_ts_stuff_null_packets(const uint8_t* ts, size_t n, size_t target_packets, uint8_t* out);
+/* The batched decoder, one wave per codeword: nstreams streams of ncw words each. A stream is
+ * ncw * n bytes; with branches, depth nonzero it is the frame-mode interleaved payload, ncw *
+ * n + D bytes, deinterleaved in the fetch (ncw * n must be a multiple of branches); with bits
+ * nonzero every byte of it is given as eight elements of one bit each, MSB first, as
+ * orion_fec_viterbi_device writes them (only bit 0 of an element is read):
+ * orion_rs_decode_stream_len elements in all. msgs [nstreams][ncw][k], status [nstreams][ncw];
+ * both equal orion_rs_decode_counted of the words, for every input. With derandomize nonzero
+ * (k = 188 only) the messages, those of uncorrectable words included, go through
+ * orion_rs_ts_energy_disperse per stream. Host slices (synchronous) or device buffers on a
+ * stream (status 4-byte aligned). */
+size_t orion_rs_decode_stream_len(size_t n, size_t n_parity, size_t ncw, int bits, size_t branches, size_t depth);
+int orion_rs_decode_batch(size_t n, size_t n_parity, const uint8_t* in, size_t nstreams, size_t ncw, int bits,
+                          size_t branches, size_t depth, int derandomize, uint8_t* msgs, int32_t* status);
+int orion_rs_decode_batch_device(size_t n, size_t n_parity, const uint8_t* in, size_t nstreams, size_t ncw, int bits,
+                                 size_t branches, size_t depth, int derandomize, uint8_t* msgs, int32_t* status,
+                                 void* stream);
+/* The batched encoder: msgs [nstreams][ncw][k] -> cws [nstreams][ncw][n], the bytes of
+ * orion_rs_encode; with disperse nonzero (k = 188 only) of orion_rs_ts_energy_disperse of each
+ * stream's messages. */
+int orion_rs_encode_batch(size_t n, size_t n_parity, const uint8_t* msgs, size_t nstreams, size_t ncw, int disperse,
+                          uint8_t* cws);
+int orion_rs_encode_batch_device(size_t n, size_t n_parity, const uint8_t* msgs, size_t nstreams, size_t ncw,
+                                 int disperse, uint8_t* cws, void* stream);
+/* The frame-mode interleaver, one thread per output element: in [nstreams][len] -> out
+ * [nstreams][orion_rs_forney_interleave_len], the bytes of orion_rs_forney_frame_interleave,
+ * with bits nonzero unpacked to one bit per element, MSB first (what
+ * orion_fec_conv_encode_batch_device reads). */
+size_t orion_rs_forney_interleave_len(size_t branches, size_t depth, size_t len, int bits);
+int orion_rs_forney_interleave_batch(size_t branches, size_t depth, const uint8_t* in, size_t nstreams, size_t len,
+                                     int bits, uint8_t* out);
+int orion_rs_forney_interleave_batch_device(size_t branches, size_t depth, const uint8_t* in, size_t nstreams,
+                                            size_t len, int bits, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

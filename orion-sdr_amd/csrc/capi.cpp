@@ -17,6 +17,8 @@
 #include "osc.hpp"
 #include "psk31.hpp"
 #include "psk31_blocks.hpp"
+#include "rs.hpp"
+#include "rs_blocks.hpp"
 #include "scan_blocks.hpp"
 #include "sync_blocks.hpp"
 
@@ -53,6 +55,15 @@ struct orion_psk31_demod_bank {
   orion::Psk31DemodBank impl;
   orion_psk31_demod_bank(float fs, const orion::psk31::Stream* streams, size_t nstreams, size_t nch)
       : impl(fs, streams, nstreams, nch) {}
+};
+struct orion_rs_forney {
+  orion::rs::ConvInterleaver impl;
+};
+struct orion_rs_pn_stream {
+  orion::rs::PnScramblerStream impl;
+};
+struct orion_rs_dispersal {
+  orion::rs::DvbTEnergyDispersal impl;
 };
 struct orion_ofdm_config {
   orion::ofdm::Config impl;
@@ -142,6 +153,35 @@ int fec_block(size_t rows, size_t cols, const T* in, T* out, bool inverse) {
     return ORION_OK;
   });
 }
+
+// a handle from a constructor that may throw
+template <class F>
+auto make_handle(F&& f) -> decltype(f()) {
+  try {
+    return f();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+template <class F>
+size_t size_or_zero(F&& f) {
+  try {
+    return f();
+  } catch (const std::exception& e) {
+    fail(ORION_E_ARG, e.what());
+    return 0;
+  }
+}
+orion::RsFusion rs_fusion(int bits, size_t branches, size_t depth, int disperse) {
+  orion::RsFusion f;
+  f.bits = bits != 0;
+  f.branches = branches;
+  f.depth = depth;
+  f.disperse = disperse != 0;
+  return f;
+}
+constexpr size_t kRsMaxHostWords = size_t(1) << 32;
 }  // namespace
 
 extern "C" {
@@ -1940,6 +1980,258 @@ int orion_fec_deinterleave_llrs(size_t rows, size_t cols, const float* llr, size
   return guarded([&] {
     const std::vector<float> v = orion::fec::BlockInterleaver(rows, cols).deinterleave_llrs(llr, n);
     if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(float));
+    return ORION_OK;
+  });
+}
+
+/* ---- the outer code (rs.hpp, k_rs.hip) ---- */
+int orion_rs_gf_tables(uint8_t* exp, uint8_t* log) {
+  if (!exp || !log) return fail(ORION_E_NULL, "null buffer");
+  const orion::rs::GfTables& t = orion::rs::Gf256::shared().tables();
+  std::memcpy(exp, t.exp, sizeof t.exp);
+  std::memcpy(log, t.log, sizeof t.log);
+  return ORION_OK;
+}
+int orion_rs_gf_mul(unsigned a, unsigned b) {
+  if (a > 255 || b > 255) return fail(ORION_E_ARG, "gf: an element is 0..255");
+  return orion::rs::Gf256::shared().mul(static_cast<uint8_t>(a), static_cast<uint8_t>(b));
+}
+int orion_rs_gf_div(unsigned a, unsigned b) {
+  if (a > 255 || b > 255) return fail(ORION_E_ARG, "gf: an element is 0..255");
+  return guarded([&] { return int(orion::rs::Gf256::shared().div(static_cast<uint8_t>(a), static_cast<uint8_t>(b))); });
+}
+int orion_rs_gf_inv(unsigned a) {
+  if (a > 255) return fail(ORION_E_ARG, "gf: an element is 0..255");
+  return guarded([&] { return int(orion::rs::Gf256::shared().inv(static_cast<uint8_t>(a))); });
+}
+int orion_rs_gf_pow(unsigned a, size_t n) {
+  if (a > 255) return fail(ORION_E_ARG, "gf: an element is 0..255");
+  return orion::rs::Gf256::shared().pow(static_cast<uint8_t>(a), n);
+}
+int orion_rs_gf_exp_of(size_t i) { return orion::rs::Gf256::shared().exp_of(i); }
+int orion_rs_generator(size_t n, size_t n_parity, uint8_t* out) {
+  if (!out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::rs::ReedSolomon code(n, n_parity);
+    std::memcpy(out, code.generator().data(), code.generator().size());
+    return ORION_OK;
+  });
+}
+int orion_rs_encode(size_t n, size_t n_parity, const uint8_t* msgs, size_t nwords, uint8_t* cws) {
+  if (nwords && (!msgs || !cws)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "rs: nwords above 2^32");
+  return guarded([&] {
+    const orion::rs::ReedSolomon code(n, n_parity);
+    if (n_parity == 0) throw std::invalid_argument("rs encode: a code without parity symbols has no shift register");
+    for (size_t w = 0; w < nwords; ++w) code.encode(msgs + w * code.k(), cws + w * n);
+    return ORION_OK;
+  });
+}
+int orion_rs_decode_counted(size_t n, size_t n_parity, const uint8_t* words, size_t nwords, uint8_t* msgs,
+                            int32_t* status) {
+  if (nwords && (!words || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "rs: nwords above 2^32");
+  return guarded([&] {
+    const orion::rs::ReedSolomon code(n, n_parity);
+    for (size_t w = 0; w < nwords; ++w) status[w] = code.decode_counted(words + w * n, msgs + w * code.k());
+    return ORION_OK;
+  });
+}
+orion_rs_forney* orion_rs_forney_new(size_t branches, size_t depth, int inverse) {
+  return make_handle([&]() -> orion_rs_forney* {
+    if (inverse) return new orion_rs_forney{orion::rs::ConvDeinterleaver(branches, depth)};
+    return new orion_rs_forney{orion::rs::ConvInterleaver(branches, depth)};
+  });
+}
+void orion_rs_forney_free(orion_rs_forney* f) { delete f; }
+int orion_rs_forney_feed(orion_rs_forney* f, const uint8_t* in, size_t n, uint8_t* out) {
+  if (!f || (n && (!in || !out))) return fail(ORION_E_NULL, "null handle or buffer");
+  f->impl.feed(in, n, out);
+  return ORION_OK;
+}
+int orion_rs_forney_flush(orion_rs_forney* f, uint8_t* out) {
+  if (!f || (f->impl.roundtrip_delay() && !out)) return fail(ORION_E_NULL, "null handle or buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> v = f->impl.flush();
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_rs_forney_reset(orion_rs_forney* f) {
+  if (!f) return fail(ORION_E_NULL, "null handle");
+  f->impl.reset();
+  return ORION_OK;
+}
+size_t orion_rs_forney_delay(size_t branches, size_t depth) {
+  return size_or_zero([&] { return orion::rs::conv_roundtrip_delay(branches, depth); });
+}
+size_t orion_rs_forney_frame_len(size_t branches, size_t depth, size_t n) {
+  return size_or_zero([&] { return orion::rs::forney_frame_len(branches, depth, n); });
+}
+int orion_rs_forney_frame_interleave(size_t branches, size_t depth, const uint8_t* bytes, size_t n, uint8_t* out) {
+  if ((n && !bytes) || !out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::rs::forney_frame_interleave(branches, depth, bytes, n);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_rs_forney_frame_deinterleave(size_t branches, size_t depth, const uint8_t* bytes, size_t total,
+                                       uint8_t* out) {
+  if (total && (!bytes || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::rs::forney_frame_deinterleave(branches, depth, bytes, total);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_rs_pn_scramble(uint32_t taps, uint32_t width, uint32_t seed, uint8_t* data, size_t n) {
+  if (n && !data) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs::PnScrambler(taps, width, seed).scramble(data, n);
+    return ORION_OK;
+  });
+}
+orion_rs_pn_stream* orion_rs_pn_stream_new(uint32_t taps, uint32_t width, uint32_t seed) {
+  return make_handle([&] { return new orion_rs_pn_stream{orion::rs::PnScramblerStream(taps, width, seed)}; });
+}
+void orion_rs_pn_stream_free(orion_rs_pn_stream* s) { delete s; }
+int orion_rs_pn_stream_feed(orion_rs_pn_stream* s, uint8_t* data, size_t n) {
+  if (!s || (n && !data)) return fail(ORION_E_NULL, "null handle or buffer");
+  s->impl.feed_in_place(data, n);
+  return ORION_OK;
+}
+int orion_rs_pn_stream_reset(orion_rs_pn_stream* s) {
+  if (!s) return fail(ORION_E_NULL, "null handle");
+  s->impl.reset();
+  return ORION_OK;
+}
+orion_rs_dispersal* orion_rs_dispersal_new(void) {
+  return make_handle([&] { return new orion_rs_dispersal{}; });
+}
+void orion_rs_dispersal_free(orion_rs_dispersal* d) { delete d; }
+int orion_rs_dispersal_feed(orion_rs_dispersal* d, uint8_t* data, size_t n) {
+  if (!d || (n && !data)) return fail(ORION_E_NULL, "null handle or buffer");
+  d->impl.feed_in_place(data, n);
+  return ORION_OK;
+}
+int orion_rs_dispersal_advance_byte(orion_rs_dispersal* d) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  d->impl.advance_byte();
+  return ORION_OK;
+}
+int orion_rs_dispersal_reset(orion_rs_dispersal* d) {
+  if (!d) return fail(ORION_E_NULL, "null handle");
+  d->impl.reset();
+  return ORION_OK;
+}
+int orion_rs_ts_energy_disperse(uint8_t* packets, size_t n) {
+  if (n && !packets) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs::ts_energy_disperse(packets, n);
+    return ORION_OK;
+  });
+}
+int orion_rs_ts_dispersal_mask(uint8_t* out) {
+  if (!out) return fail(ORION_E_NULL, "null buffer");
+  const orion::rs::TsDispersalMask& mask = orion::rs::ts_dispersal_mask();
+  std::memcpy(out, mask.m, sizeof mask.m);
+  return ORION_OK;
+}
+size_t orion_rs_ts_packetized_len(size_t n) {
+  if (n > (size_t(1) << 40)) {
+    fail(ORION_E_ARG, "ts: n above 2^40");
+    return 0;
+  }
+  return std::max<size_t>((n + orion::rs::kTsPayloadLen - 1) / orion::rs::kTsPayloadLen, 1) * orion::rs::kTsPacketLen;
+}
+int orion_rs_ts_packetize(const uint8_t* payload, size_t n, uint8_t* out) {
+  if ((n && !payload) || !out) return fail(ORION_E_NULL, "null buffer");
+  if (n > (size_t(1) << 40)) return fail(ORION_E_ARG, "ts: n above 2^40");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::rs::ts_packetize(payload, n);
+    std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_rs_ts_depacketize(const uint8_t* packets, size_t n, uint8_t* out) {
+  if (n && (!packets || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::rs::ts_depacketize(packets, n);
+    std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+int orion_rs_ts_null_packet(uint8_t* out) {
+  if (!out) return fail(ORION_E_NULL, "null buffer");
+  orion::rs::ts_null_packet(out);
+  return ORION_OK;
+}
+int orion_rs_ts_stuff_null_packets(const uint8_t* ts, size_t n, size_t target_packets, uint8_t* out) {
+  if ((n && !ts) || ((n || target_packets) && !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    std::vector<uint8_t> v(ts, ts + n);
+    orion::rs::ts_stuff_null_packets(v, target_packets);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return ORION_OK;
+  });
+}
+size_t orion_rs_decode_stream_len(size_t n, size_t n_parity, size_t ncw, int bits, size_t branches, size_t depth) {
+  return size_or_zero([&] { return orion::rs_decode_stream_len(n, n_parity, ncw, rs_fusion(bits, branches, depth, 0)); });
+}
+int orion_rs_decode_batch(size_t n, size_t n_parity, const uint8_t* in, size_t nstreams, size_t ncw, int bits,
+                          size_t branches, size_t depth, int derandomize, uint8_t* msgs, int32_t* status) {
+  if (nstreams && (!in || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs_decode_batch_host(n, n_parity, in, nstreams, ncw, rs_fusion(bits, branches, depth, derandomize), msgs,
+                                status);
+    return ORION_OK;
+  });
+}
+int orion_rs_decode_batch_device(size_t n, size_t n_parity, const uint8_t* in, size_t nstreams, size_t ncw, int bits,
+                                 size_t branches, size_t depth, int derandomize, uint8_t* msgs, int32_t* status,
+                                 void* stream) {
+  if (nstreams && (!in || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs_decode_batch(n, n_parity, in, nstreams, ncw, rs_fusion(bits, branches, depth, derandomize), msgs, status,
+                           static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_rs_encode_batch(size_t n, size_t n_parity, const uint8_t* msgs, size_t nstreams, size_t ncw, int disperse,
+                          uint8_t* cws) {
+  if (nstreams && (!msgs || !cws)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs_encode_batch_host(n, n_parity, msgs, nstreams, ncw, rs_fusion(0, 0, 0, disperse), cws);
+    return ORION_OK;
+  });
+}
+int orion_rs_encode_batch_device(size_t n, size_t n_parity, const uint8_t* msgs, size_t nstreams, size_t ncw,
+                                 int disperse, uint8_t* cws, void* stream) {
+  if (nstreams && (!msgs || !cws)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::rs_encode_batch(n, n_parity, msgs, nstreams, ncw, rs_fusion(0, 0, 0, disperse), cws,
+                           static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_rs_forney_interleave_len(size_t branches, size_t depth, size_t len, int bits) {
+  return size_or_zero([&] { return orion::forney_interleave_stream_len(branches, depth, len, bits != 0); });
+}
+int orion_rs_forney_interleave_batch(size_t branches, size_t depth, const uint8_t* in, size_t nstreams, size_t len,
+                                     int bits, uint8_t* out) {
+  if (nstreams && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::forney_interleave_batch_host(branches, depth, in, nstreams, len, bits != 0, out);
+    return ORION_OK;
+  });
+}
+int orion_rs_forney_interleave_batch_device(size_t branches, size_t depth, const uint8_t* in, size_t nstreams,
+                                            size_t len, int bits, uint8_t* out, void* stream) {
+  if (nstreams && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::forney_interleave_batch(branches, depth, in, nstreams, len, bits != 0, out,
+                                   static_cast<hipStream_t>(stream));
     return ORION_OK;
   });
 }

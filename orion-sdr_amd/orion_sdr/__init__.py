@@ -3288,3 +3288,509 @@ def conv_viterbi_batch(llr, info_bits, rate, code="k5", interleaver=None, stream
     bits = np.zeros((ns, n), np.uint8)
     _arg_check(_L.orion_fec_viterbi(c, r, llr.ctypes.data, ns, nl, n, rows, cols, bits.ctypes.data))
     return bits
+
+
+# ---- the outer code: Reed-Solomon, the Forney interleaver, scramblers, the TS layer (src/fec,
+# src/waveform/dvb_t.rs, dvb_t_ts.rs) ----
+def _rs_sigs():
+    vp, sz, i, u, u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint32
+    sig = {
+        "orion_rs_gf_tables": (i, [vp, vp]), "orion_rs_gf_mul": (i, [u, u]), "orion_rs_gf_div": (i, [u, u]),
+        "orion_rs_gf_inv": (i, [u]), "orion_rs_gf_pow": (i, [u, sz]), "orion_rs_gf_exp_of": (i, [sz]),
+        "orion_rs_generator": (i, [sz, sz, vp]), "orion_rs_encode": (i, [sz, sz, vp, sz, vp]),
+        "orion_rs_decode_counted": (i, [sz, sz, vp, sz, vp, vp]),
+        "orion_rs_forney_new": (vp, [sz, sz, i]), "orion_rs_forney_free": (None, [vp]),
+        "orion_rs_forney_feed": (i, [vp, vp, sz, vp]), "orion_rs_forney_flush": (i, [vp, vp]),
+        "orion_rs_forney_reset": (i, [vp]), "orion_rs_forney_delay": (sz, [sz, sz]),
+        "orion_rs_forney_frame_len": (sz, [sz, sz, sz]),
+        "orion_rs_forney_frame_interleave": (i, [sz, sz, vp, sz, vp]),
+        "orion_rs_forney_frame_deinterleave": (i, [sz, sz, vp, sz, vp]),
+        "orion_rs_pn_scramble": (i, [u32, u32, u32, vp, sz]),
+        "orion_rs_pn_stream_new": (vp, [u32, u32, u32]), "orion_rs_pn_stream_free": (None, [vp]),
+        "orion_rs_pn_stream_feed": (i, [vp, vp, sz]), "orion_rs_pn_stream_reset": (i, [vp]),
+        "orion_rs_dispersal_new": (vp, []), "orion_rs_dispersal_free": (None, [vp]),
+        "orion_rs_dispersal_feed": (i, [vp, vp, sz]), "orion_rs_dispersal_advance_byte": (i, [vp]),
+        "orion_rs_dispersal_reset": (i, [vp]),
+        "orion_rs_ts_energy_disperse": (i, [vp, sz]), "orion_rs_ts_dispersal_mask": (i, [vp]),
+        "orion_rs_ts_packetized_len": (sz, [sz]), "orion_rs_ts_packetize": (i, [vp, sz, vp]),
+        "orion_rs_ts_depacketize": (i, [vp, sz, vp]), "orion_rs_ts_null_packet": (i, [vp]),
+        "orion_rs_ts_stuff_null_packets": (i, [vp, sz, sz, vp]),
+        "orion_rs_decode_stream_len": (sz, [sz, sz, sz, i, sz, sz]),
+        "orion_rs_decode_batch": (i, [sz, sz, vp, sz, sz, i, sz, sz, i, vp, vp]),
+        "orion_rs_decode_batch_device": (i, [sz, sz, vp, sz, sz, i, sz, sz, i, vp, vp, vp]),
+        "orion_rs_encode_batch": (i, [sz, sz, vp, sz, sz, i, vp]),
+        "orion_rs_encode_batch_device": (i, [sz, sz, vp, sz, sz, i, vp, vp]),
+        "orion_rs_forney_interleave_len": (sz, [sz, sz, sz, i]),
+        "orion_rs_forney_interleave_batch": (i, [sz, sz, vp, sz, sz, i, vp]),
+        "orion_rs_forney_interleave_batch_device": (i, [sz, sz, vp, sz, sz, i, vp, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_rs_sigs()
+
+__all__ += ["Gf256", "ReedSolomon", "RsUncorrectable", "ConvInterleaver", "ConvDeinterleaver", "PnScrambler",
+            "PnScramblerStream", "DvbTEnergyDispersal", "forney_frame_interleave", "forney_frame_deinterleave",
+            "ts_energy_disperse", "ts_packetize", "ts_depacketize", "ts_null_packet", "ts_stuff_null_packets",
+            "rs_encode_batch", "rs_decode_batch", "forney_interleave_batch", "TS_PACKET_LEN"]
+TS_PACKET_LEN = 188
+
+
+def _bytes_arg(x, what="data", ndim=1) -> np.ndarray:
+    if isinstance(x, (bytes, bytearray)) and ndim == 1:
+        x = np.frombuffer(bytes(x), np.uint8)
+    if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.ndim != ndim:
+        raise ValueError(f"{what}: expected a {ndim}-D uint8 array")
+    return np.ascontiguousarray(x)
+
+
+def _gf_elem(rc: int) -> int:
+    if rc < 0:
+        raise ValueError(_err())
+    return rc
+
+
+class Gf256:
+    """GF(2^8) under 0x11D with generator 2 (fec/gf.rs), host only."""
+
+    @staticmethod
+    def tables():
+        """(exp (512,), log (256,)): exp[i] = 2^i with the cycle of 255 repeated, log[0] unused."""
+        e, lg = np.zeros(512, np.uint8), np.zeros(256, np.uint8)
+        _check(_L.orion_rs_gf_tables(e.ctypes.data, lg.ctypes.data))
+        return e, lg
+
+    @staticmethod
+    def _u(a) -> int:
+        a = int(a)
+        if not 0 <= a <= 255:
+            raise ValueError("gf: an element is 0..255")
+        return a
+
+    @staticmethod
+    def add(a, b) -> int:
+        return Gf256._u(a) ^ Gf256._u(b)
+
+    @staticmethod
+    def mul(a, b) -> int:
+        return _gf_elem(_L.orion_rs_gf_mul(Gf256._u(a), Gf256._u(b)))
+
+    @staticmethod
+    def div(a, b) -> int:
+        return _gf_elem(_L.orion_rs_gf_div(Gf256._u(a), Gf256._u(b)))
+
+    @staticmethod
+    def inv(a) -> int:
+        return _gf_elem(_L.orion_rs_gf_inv(Gf256._u(a)))
+
+    @staticmethod
+    def pow(a, n) -> int:
+        n = int(n)
+        if n < 0:
+            raise ValueError("gf pow: n >= 0")
+        return _gf_elem(_L.orion_rs_gf_pow(Gf256._u(a), n if n < 1 << 63 else n % 255 + 255))
+
+    @staticmethod
+    def exp_of(i) -> int:
+        i = int(i)
+        if i < 0:
+            raise ValueError("gf exp_of: i >= 0")
+        return _gf_elem(_L.orion_rs_gf_exp_of(i % 255))
+
+
+class RsUncorrectable(ValueError):
+    """ReedSolomon.decode of an uncorrectable word; message is the systematic prefix received[:k]."""
+
+    def __init__(self, message):
+        super().__init__("codeword is uncorrectable")
+        self.message = message
+
+
+class ReedSolomon:
+    """ReedSolomon (fec/reed_solomon.rs), host only: n codeword bytes, n_parity parity bytes
+    (1 <= n <= 255, n_parity < n), t = n_parity // 2. Byte 0 is the highest-degree symbol."""
+
+    def __init__(self, n, n_parity):
+        n, n_parity = int(n), int(n_parity)
+        if n < 1 or n > 255 or n_parity < 0 or n_parity >= n:
+            raise ValueError("rs: code length n out of range 1..=255 or too short for the parity symbols")
+        self.n, self.n_parity, self.k, self.t = n, n_parity, n - n_parity, n_parity // 2
+
+    @classmethod
+    def dvb(cls):
+        """DVB-T's RS(204, 188), t = 8."""
+        return cls(204, 16)
+
+    @property
+    def parity_bytes(self) -> int:
+        return self.n_parity
+
+    def generator(self) -> np.ndarray:
+        """g(x) = prod (x - 2^i), i < n_parity, low degree first."""
+        out = np.zeros(self.n_parity + 1, np.uint8)
+        _arg_check(_L.orion_rs_generator(self.n, self.n_parity, out.ctypes.data))
+        return out
+
+    def _words(self, x, width, what):
+        if isinstance(x, (bytes, bytearray)):
+            x = np.frombuffer(bytes(x), np.uint8)
+        if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.ndim not in (1, 2) or x.shape[-1] != width:
+            raise ValueError(f"{what}: expected uint8 ({width},) or (nwords, {width})")
+        return np.ascontiguousarray(x), x.ndim == 1
+
+    def encode(self, message) -> np.ndarray:
+        """message (k,) or (nwords, k) -> codeword(s) message | parity."""
+        m, one = self._words(message, self.k, "message")
+        out = np.zeros(m.shape[:-1] + (self.n,), np.uint8)
+        _arg_check(_L.orion_rs_encode(self.n, self.n_parity, m.ctypes.data, m.size // self.k, out.ctypes.data))
+        return out
+
+    def decode_counted(self, received):
+        """decode_counted (reed_solomon.rs:141-233): received (n,) -> (message (k,), count),
+        or (nwords, n) -> (messages (nwords, k), counts (nwords,) int32). count is the number of
+        codeword bytes corrected, parity included; -1: uncorrectable, the message is then
+        received[:k]."""
+        r, one = self._words(received, self.n, "received")
+        msgs = np.zeros(r.shape[:-1] + (self.k,), np.uint8)
+        status = np.zeros(r.size // self.n, np.int32)
+        _arg_check(_L.orion_rs_decode_counted(self.n, self.n_parity, r.ctypes.data, status.size, msgs.ctypes.data,
+                                              status.ctypes.data))
+        return (msgs, int(status[0])) if one else (msgs, status)
+
+    def decode(self, received) -> np.ndarray:
+        """decode (reed_solomon.rs:118-120) of one word; raises RsUncorrectable (carrying
+        received[:k]) where the reference returns Uncorrectable."""
+        r = _bytes_arg(received, "received")
+        msg, count = self.decode_counted(r)
+        if count < 0:
+            raise RsUncorrectable(msg)
+        return msg
+
+
+def _forney_dims(branches, depth):
+    branches, depth = int(branches), int(depth)
+    if branches < 1 or depth < 1:
+        raise ValueError("convolutional interleaver dimensions must be nonzero")
+    if branches * branches * depth > 1 << 24:
+        raise ValueError("convolutional interleaver: branches^2 * depth above 2^24")
+    return branches, depth
+
+
+class ConvInterleaver:
+    """ConvInterleaver (fec/interleaver.rs:133-220), host only: the streaming Forney byte
+    interleaver of `branches` branches, branch j a FIFO of j * depth bytes. feed is 1:1 in
+    length and carries state across calls; flush feeds roundtrip_delay zeros; reset restarts."""
+
+    _inverse = 0
+
+    def __init__(self, branches, depth):
+        self.branches, self.depth = _forney_dims(branches, depth)
+        self._h = _L.orion_rs_forney_new(self.branches, self.depth, self._inverse)
+        if not self._h:
+            raise ValueError(_err())
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _L.orion_rs_forney_free(self._h)
+            self._h = None
+
+    @classmethod
+    def dvb_t(cls):
+        """DVB-T's outer interleaver: I = 12, M = 17."""
+        return cls(12, 17)
+
+    @property
+    def roundtrip_delay(self) -> int:
+        return self.branches * (self.branches - 1) * self.depth
+
+    def reset(self):
+        _check(_L.orion_rs_forney_reset(self._h))
+
+    def feed(self, data) -> np.ndarray:
+        d = _bytes_arg(data)
+        out = np.zeros(d.size, np.uint8)
+        _check(_L.orion_rs_forney_feed(self._h, d.ctypes.data, d.size, out.ctypes.data))
+        return out
+
+    def flush(self) -> np.ndarray:
+        out = np.zeros(self.roundtrip_delay, np.uint8)
+        _check(_L.orion_rs_forney_flush(self._h, out.ctypes.data))
+        return out
+
+
+class ConvDeinterleaver(ConvInterleaver):
+    """ConvDeinterleaver (fec/interleaver.rs:226-305): the inverse, branch j a FIFO of
+    (branches - 1 - j) * depth bytes; it reproduces the interleaver's input from output byte
+    roundtrip_delay on."""
+
+    _inverse = 1
+
+
+def forney_frame_interleave(data, branches, depth) -> np.ndarray:
+    """interleave_bits' Convolutional arm in bytes (modulate/ofdm_frame.rs:464-478), host only:
+    data zero-padded to a multiple of branches bytes through a fresh interleaver, then the
+    flush: round_up(n, branches) + branches (branches - 1) depth bytes."""
+    branches, depth = _forney_dims(branches, depth)
+    d = _bytes_arg(data)
+    out = np.zeros(int(_L.orion_rs_forney_frame_len(branches, depth, d.size)), np.uint8)
+    _arg_check(_L.orion_rs_forney_frame_interleave(branches, depth, d.ctypes.data, d.size, out.ctypes.data))
+    return out
+
+
+def forney_frame_deinterleave(data, branches, depth) -> np.ndarray:
+    """deinterleave_bits' Convolutional arm in bytes (demodulate/ofdm_frame.rs:399-415), host
+    only: data through a fresh deinterleaver, of which the bytes from the round-trip delay on
+    are the padded payload (nothing when data is no longer than the delay)."""
+    branches, depth = _forney_dims(branches, depth)
+    d = _bytes_arg(data)
+    out = np.zeros(max(d.size - branches * (branches - 1) * depth, 0), np.uint8)
+    _arg_check(_L.orion_rs_forney_frame_deinterleave(branches, depth, d.ctypes.data, d.size, out.ctypes.data))
+    return out
+
+
+def _lfsr_args(taps, width, seed):
+    taps, width, seed = int(taps), int(width), int(seed)
+    if not 2 <= width <= 32:
+        raise ValueError("LFSR width must be in 2..=32")
+    mask = (1 << width) - 1
+    if seed == 0:
+        raise ValueError("LFSR seed must be nonzero")
+    if seed < 0 or seed & ~mask or taps < 0 or taps & ~mask:
+        raise ValueError("LFSR seed and taps must fit in `width` bits")
+    return taps, width, seed
+
+
+class PnScrambler:
+    """PnScrambler (fec/scrambler.rs:39-104), host only: an additive Fibonacci LFSR whitener,
+    data bits LSB first, restarted from seed on every scramble call (self-inverse)."""
+
+    def __init__(self, taps, width, seed):
+        self.taps, self.width, self.seed = _lfsr_args(taps, width, seed)
+
+    def scramble(self, data) -> np.ndarray:
+        out = _bytes_arg(data).copy()
+        _arg_check(_L.orion_rs_pn_scramble(self.taps, self.width, self.seed, out.ctypes.data, out.size))
+        return out
+
+    def into_stream(self):
+        return PnScramblerStream(self.taps, self.width, self.seed)
+
+
+class PnScramblerStream:
+    """PnScramblerStream (fec/scrambler.rs:133-195), host only: the same whitener with the
+    register carried across feed calls; reset restarts from seed."""
+
+    def __init__(self, taps, width, seed):
+        self.taps, self.width, self.seed = _lfsr_args(taps, width, seed)
+        self._h = _L.orion_rs_pn_stream_new(self.taps, self.width, self.seed)
+        if not self._h:
+            raise ValueError(_err())
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _L.orion_rs_pn_stream_free(self._h)
+            self._h = None
+
+    def reset(self):
+        _check(_L.orion_rs_pn_stream_reset(self._h))
+
+    def feed(self, data) -> np.ndarray:
+        out = _bytes_arg(data).copy()
+        _check(_L.orion_rs_pn_stream_feed(self._h, out.ctypes.data, out.size))
+        return out
+
+
+class DvbTEnergyDispersal:
+    """DvbTEnergyDispersal (waveform/dvb_t.rs:30-110), host only: the PRBS 1 + X^14 + X^15 from
+    100101010000000 XORed over the data MSB first, the register carried across feed calls;
+    advance_byte clocks eight steps without output; reset reloads the init."""
+
+    def __init__(self):
+        self._h = _L.orion_rs_dispersal_new()
+        if not self._h:
+            raise OrionError(f"orion_sdr: construction failed: {_err()}")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _L.orion_rs_dispersal_free(self._h)
+            self._h = None
+
+    def reset(self):
+        _check(_L.orion_rs_dispersal_reset(self._h))
+
+    def advance_byte(self):
+        _check(_L.orion_rs_dispersal_advance_byte(self._h))
+
+    def feed(self, data) -> np.ndarray:
+        out = _bytes_arg(data).copy()
+        _check(_L.orion_rs_dispersal_feed(self._h, out.ctypes.data, out.size))
+        return out
+
+
+def ts_energy_disperse(packets) -> np.ndarray:
+    """ts_energy_disperse (waveform/dvb_t_ts.rs:53-79), host only, returning a copy: whole
+    188-byte packets; the PRBS restarts every eight packets, the first sync byte of a group
+    flips 0x47 <-> 0xB8, the others are clocked over, the payloads are whitened. Self-inverse."""
+    out = _bytes_arg(packets, "packets").copy()
+    _arg_check(_L.orion_rs_ts_energy_disperse(out.ctypes.data, out.size))
+    return out
+
+
+def ts_packetize(payload) -> np.ndarray:
+    """ts_packetize (dvb_t_ts.rs:87-100): max(1, ceil(n / 187)) packets of 0x47 + 187 payload
+    bytes, the last zero-padded."""
+    p = _bytes_arg(payload, "payload")
+    out = np.zeros(int(_L.orion_rs_ts_packetized_len(p.size)), np.uint8)
+    _arg_check(_L.orion_rs_ts_packetize(p.ctypes.data, p.size, out.ctypes.data))
+    return out
+
+
+def ts_depacketize(packets):
+    """ts_depacketize (dvb_t_ts.rs:139-148): the payloads of whole packets; None when packets
+    is empty or no whole number of packets."""
+    p = _bytes_arg(packets, "packets")
+    if p.size == 0 or p.size % TS_PACKET_LEN:
+        return None
+    out = np.zeros(p.size // TS_PACKET_LEN * 187, np.uint8)
+    _arg_check(_L.orion_rs_ts_depacketize(p.ctypes.data, p.size, out.ctypes.data))
+    return out
+
+
+def ts_null_packet() -> np.ndarray:
+    """ts_null_packet (dvb_t_ts.rs:109-116): 47 1F FF 10 and 184 bytes of 0xFF."""
+    out = np.zeros(TS_PACKET_LEN, np.uint8)
+    _check(_L.orion_rs_ts_null_packet(out.ctypes.data))
+    return out
+
+
+def ts_stuff_null_packets(ts, target_packets) -> np.ndarray:
+    """ts_stuff_null_packets (dvb_t_ts.rs:123-133), returning a copy: ts (whole packets)
+    followed by null packets up to target_packets packets."""
+    t = _bytes_arg(ts, "ts")
+    target_packets = int(target_packets)
+    if t.size % TS_PACKET_LEN or target_packets < 0 or target_packets > 1 << 32:
+        raise ValueError("ts_stuff_null_packets: ts must be whole TS packets, 0 <= target_packets <= 2^32")
+    out = np.zeros(max(t.size // TS_PACKET_LEN, target_packets) * TS_PACKET_LEN, np.uint8)
+    _arg_check(_L.orion_rs_ts_stuff_null_packets(t.ctypes.data, t.size, target_packets, out.ctypes.data))
+    return out
+
+
+def _rs_u8(x, what, ndims):
+    """x as a contiguous uint8 numpy array or torch CUDA tensor of one of ndims dimensions."""
+    if _is_torch(x):
+        import torch
+
+        if not x.is_cuda or not x.is_contiguous() or x.dtype != torch.uint8 or x.dim() not in ndims:
+            raise ValueError(f"{what}: a contiguous uint8 CUDA tensor of {' or '.join(map(str, ndims))} dimensions")
+        return x, True
+    if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.ndim not in ndims:
+        raise ValueError(f"{what}: expected a uint8 array of {' or '.join(map(str, ndims))} dimensions")
+    return np.ascontiguousarray(x), False
+
+
+def _rs_out(x, dev, shape, dtype):
+    if dev:
+        import torch
+
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=x.device)
+    return np.zeros(shape, getattr(np, dtype))
+
+
+def _rs_ptr(a, dev):
+    return a.data_ptr() if dev else a.ctypes.data
+
+
+def rs_encode_batch(msgs, n=204, n_parity=16, disperse=False, stream=None):
+    """Reed-Solomon encode a batch on the GPU in one launch: uint8 (nstreams, ncw, k) or (ncw,
+    k) -> (..., ncw, n), each word ReedSolomon(n, n_parity).encode of its message. disperse
+    (k = 188): each stream's messages go through ts_energy_disperse first, word c of a stream
+    being packet c. 1 <= n_parity <= 32. A numpy array (-> numpy) or a contiguous torch CUDA
+    tensor (-> a torch tensor on its device, queued on torch's current stream or on stream)."""
+    code = ReedSolomon(n, n_parity)
+    m, dev = _rs_u8(msgs, "msgs", (2, 3))
+    if m.shape[-1] != code.k:
+        raise ValueError(f"msgs: the last dimension is k = {code.k}")
+    ns, ncw = (1, int(m.shape[0])) if len(m.shape) == 2 else (int(m.shape[0]), int(m.shape[1]))
+    out = _rs_out(m, dev, tuple(m.shape[:-1]) + (code.n,), "uint8")
+    if dev:
+        _arg_check(_L.orion_rs_encode_batch_device(code.n, code.n_parity, m.data_ptr(), ns, ncw, int(bool(disperse)),
+                                                   out.data_ptr(), SyncEngine._stream(m, stream)))
+    else:
+        _arg_check(_L.orion_rs_encode_batch(code.n, code.n_parity, m.ctypes.data, ns, ncw, int(bool(disperse)),
+                                            out.ctypes.data))
+    return out
+
+
+def rs_decode_batch(x, n=204, n_parity=16, bits=False, deinterleave=None, derandomize=False, stream=None):
+    """Reed-Solomon decode a batch on the GPU in one launch, one wave per codeword: returns
+    (msgs, status), status int32 the corrected-byte count of each word or -1 for an
+    uncorrectable one (whose message is received[:k]); both equal
+    ReedSolomon(n, n_parity).decode_counted of every word. 1 <= n_parity <= 32.
+
+    Without bits and deinterleave, x is uint8 (nstreams, ncw, n) or (ncw, n) and msgs (...,
+    ncw, k), status (..., ncw). Otherwise x is one flat stream per row, (nstreams, len) or
+    (len,), and msgs is (nstreams, ncw, k) or (ncw, k): bits: every byte as eight elements of
+    one bit, MSB first (the tensor conv_viterbi_batch returns is taken as it is); deinterleave
+    = (branches, depth): the stream is forney_frame_interleave of the ncw * n codeword bytes
+    (a multiple of branches), undone in the fetch. derandomize (k = 188): the messages go
+    through ts_energy_disperse per stream, failed words included. A numpy array (-> numpy) or
+    a contiguous torch CUDA tensor (-> torch tensors on its device, queued on torch's current
+    stream or on stream)."""
+    code = ReedSolomon(n, n_parity)
+    I, M = _forney_dims(*deinterleave) if deinterleave is not None else (0, 0)
+    flat = bool(bits) or I > 0
+    a, dev = _rs_u8(x, "x", (1, 2) if flat else (2, 3))
+    if flat:
+        batched = len(a.shape) == 2
+        ns, length = (int(a.shape[0]), int(a.shape[1])) if batched else (1, int(a.shape[0]))
+        unit = 8 if bits else 1
+        payload = length // unit - I * (I - 1) * M
+        if length % unit or payload < code.n or payload % code.n:
+            raise ValueError("x: a stream is ncw * n bytes, plus the interleaver's round-trip delay, times 8 for bits")
+        ncw = payload // code.n
+        lead = (ns, ncw) if batched else (ncw,)
+    else:
+        if a.shape[-1] != code.n:
+            raise ValueError(f"x: the last dimension is n = {code.n}")
+        ns, ncw = (1, int(a.shape[0])) if len(a.shape) == 2 else (int(a.shape[0]), int(a.shape[1]))
+        lead = tuple(a.shape[:-1])
+    if ncw < 1:
+        raise ValueError("x: at least one codeword per stream")
+    msgs, status = _rs_out(a, dev, lead + (code.k,), "uint8"), _rs_out(a, dev, lead, "int32")
+    args = (code.n, code.n_parity, _rs_ptr(a, dev), ns, ncw, int(bool(bits)), I, M, int(bool(derandomize)),
+            _rs_ptr(msgs, dev), _rs_ptr(status, dev))
+    if dev:
+        _arg_check(_L.orion_rs_decode_batch_device(*args, SyncEngine._stream(a, stream)))
+    else:
+        _arg_check(_L.orion_rs_decode_batch(*args))
+    return msgs, status
+
+
+def forney_interleave_batch(x, branches, depth, bits=False, stream=None):
+    """The frame-mode Forney interleaver of a batch on the GPU in one launch: uint8 (nstreams,
+    len), (len,) or (nstreams, ncw, n) (a stream is then its ncw * n bytes) -> (nstreams, out)
+    or (out,), each row forney_frame_interleave of its stream; bits: unpacked to one bit per
+    element, MSB first, which conv_encode_batch takes as it is. A numpy array (-> numpy) or a
+    contiguous torch CUDA tensor (-> a torch tensor on its device, queued on torch's current
+    stream or on stream)."""
+    I, M = _forney_dims(branches, depth)
+    a, dev = _rs_u8(x, "x", (1, 2, 3))
+    batched = len(a.shape) > 1
+    ns = int(a.shape[0]) if batched else 1
+    length = 1
+    for d in a.shape[1 if batched else 0:]:
+        length *= int(d)
+    out_len = int(_L.orion_rs_forney_interleave_len(I, M, length, int(bool(bits))))
+    if out_len == 0:
+        raise ValueError(_err())
+    out = _rs_out(a, dev, (ns, out_len) if batched else (out_len,), "uint8")
+    if dev:
+        _arg_check(_L.orion_rs_forney_interleave_batch_device(I, M, a.data_ptr(), ns, length, int(bool(bits)),
+                                                              out.data_ptr(), SyncEngine._stream(a, stream)))
+    else:
+        _arg_check(_L.orion_rs_forney_interleave_batch(I, M, a.ctypes.data, ns, length, int(bool(bits)),
+                                                       out.ctypes.data))
+    return out
