@@ -1158,6 +1158,80 @@ int orion_rs_forney_interleave_batch(size_t branches, size_t depth, const uint8_
 int orion_rs_forney_interleave_batch_device(size_t branches, size_t depth, const uint8_t* in, size_t nstreams,
                                             size_t len, int bits, uint8_t* out, void* stream);
 
+/* ---- the COFDM frame chain's codes: the constructed LDPC family and the shortened binary BCH
+ * code (src/fec/ldpc_codes.rs, src/fec/bch.rs; ldpc_family.hpp, bch.hpp, k_ldpc_family.hip,
+ * k_bch.hip). A bad argument is ORION_E_ARG, before anything is launched. ---- */
+#define ORION_LDPCF_N512R12 0 /* N = 512, K = 256 */
+#define ORION_LDPCF_N576R23 1 /* N = 576, K = 384 */
+#define ORION_LDPCF_N512R34 2 /* N = 512, K = 384 */
+#define ORION_LDPCF_SUM_PRODUCT 0
+#define ORION_LDPCF_MIN_SUM 1
+#define ORION_LDPCF_SCALED_MIN_SUM 2 /* the message times scale */
+/* The code, built on first use and kept. dims: out [6] = N, K, M, edges, the largest check
+ * degree, the picks for which the 4-cycle guard was relaxed. graph: the Tanner graph as CSR:
+ * check_start [M + 1], check_bits [edges] (within a check the message columns ascending, then
+ * K + i, then K + i - 1), bit_start [N + 1], bit_checks [edges] (ascending) and bit_edges
+ * [edges], the index into check_bits of that bit in that check. */
+int orion_ldpcf_dims(int code, uint32_t* out);
+int orion_ldpcf_graph(int code, uint32_t* check_start, uint32_t* check_bits, uint32_t* bit_start,
+                      uint32_t* bit_checks, uint32_t* bit_edges);
+/* Host only, nwords words each. encode: msgs [nwords][K] -> cws [nwords][N], message | parity
+ * (the message elements as they are, bit 0 of each in the parity). syndrome_weight: hard
+ * [nwords][N] -> unsat [nwords]. decode_soft: llr [nwords][N], positive meaning bit 0 -> bits
+ * [nwords][K], unsat [nwords] (the smallest unsatisfied-check count seen, 0: decoded),
+ * iterations [nwords] (0: the initial decision was a codeword). */
+int orion_ldpcf_encode(int code, const uint8_t* msgs, size_t nwords, uint8_t* cws);
+int orion_ldpcf_syndrome_weight(int code, const uint8_t* hard, size_t nwords, int32_t* unsat);
+int orion_ldpcf_decode_soft(int code, const float* llr, size_t nwords, size_t max_iter, int rule, float scale,
+                            uint8_t* bits, int32_t* unsat, int32_t* iterations);
+/* The batched decoder, one wave per codeword: llr [nstreams][n_llr]; with rows, cols nonzero a
+ * stream is whole interleaver blocks and is deinterleaved in the fetch (as
+ * orion_fec_deinterleave_llrs); its nblocks = orion_ldpcf_decode_blocks words are elements 0 ..
+ * nblocks * N of that, the rest is not read. bits [nstreams][nblocks * K], unsat and iterations
+ * [nstreams][nblocks]; all equal orion_ldpcf_decode_soft of the words, for every input. Host
+ * slices (synchronous) or device buffers on a stream. */
+size_t orion_ldpcf_decode_blocks(int code, size_t n_llr, size_t rows, size_t cols);
+int orion_ldpcf_decode_batch(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows, size_t cols,
+                             size_t max_iter, int rule, float scale, uint8_t* bits, int32_t* unsat,
+                             int32_t* iterations);
+int orion_ldpcf_decode_batch_device(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows,
+                                    size_t cols, size_t max_iter, int rule, float scale, uint8_t* bits,
+                                    int32_t* unsat, int32_t* iterations, void* stream);
+/* The batched encoder: bits [nstreams][nbits] -> coded [nstreams][orion_ldpcf_encoded_len]:
+ * ceil(nbits / K) codewords, the last message zero-padded, then with rows, cols nonzero the
+ * block interleaver, zero-padded to whole blocks (as orion_fec_interleave_bits). */
+size_t orion_ldpcf_encoded_len(int code, size_t nbits, size_t rows, size_t cols);
+int orion_ldpcf_encode_batch(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows, size_t cols,
+                             uint8_t* coded);
+int orion_ldpcf_encode_batch_device(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows,
+                                    size_t cols, uint8_t* coded, void* stream);
+/* The binary BCH code over GF(2^8) correcting t bit errors, shortened to n elements of one bit
+ * each, index 0 the highest degree; host only. parity_bits: of the code of t, 0 on a bad t.
+ * generator: out [parity_bits + 1], highest degree first. encode: msgs [nwords][k] -> cws
+ * [nwords][n]. decode: words [nwords][n] -> msgs [nwords][k], status [nwords]: the bits flipped
+ * (an element is set when nonzero, a flip is ^= 1), or -max(residual syndromes, roots found)
+ * <= -1 for an uncorrectable word, whose message is then words[:k]; locator_len (optional)
+ * [nwords]: entries of the Berlekamp-Massey locator vector, 0 for a clean word. */
+size_t orion_bch_parity_bits(size_t t);
+int orion_bch_generator(size_t n, size_t t, uint8_t* out);
+int orion_bch_encode(size_t n, size_t t, const uint8_t* msgs, size_t nwords, uint8_t* cws);
+int orion_bch_decode(size_t n, size_t t, const uint8_t* words, size_t nwords, uint8_t* msgs, int32_t* status,
+                     int32_t* locator_len);
+/* The batched coder of the frame chain, one wave per word, for the code of t (1 .. 31) over
+ * info_bits information bits, n = info_bits + parity_bits. decode: in [nstreams][nb], ncw = nb
+ * / n >= 1 words per stream, the tail ignored -> msgs [nstreams][ncw * info_bits], status
+ * [nstreams][ncw], both equal to orion_bch_decode of the words. encode: bits [nstreams][nbits]
+ * -> coded [nstreams][ceil(nbits / info_bits) * n], the last message zero-padded. Host slices
+ * (synchronous) or device buffers on a stream (status 4-byte aligned). */
+int orion_bch_decode_batch(size_t t, size_t info_bits, const uint8_t* in, size_t nstreams, size_t nb, uint8_t* msgs,
+                           int32_t* status);
+int orion_bch_decode_batch_device(size_t t, size_t info_bits, const uint8_t* in, size_t nstreams, size_t nb,
+                                  uint8_t* msgs, int32_t* status, void* stream);
+int orion_bch_encode_batch(size_t t, size_t info_bits, const uint8_t* bits, size_t nstreams, size_t nbits,
+                           uint8_t* coded);
+int orion_bch_encode_batch_device(size_t t, size_t info_bits, const uint8_t* bits, size_t nstreams, size_t nbits,
+                                  uint8_t* coded, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,14 @@
 #include <string>
 #include <vector>
 
+#include "bch.hpp"
+#include "bch_blocks.hpp"
 #include "blocks.hpp"
 #include "fec.hpp"
 #include "fec_blocks.hpp"
 #include "ldpc.hpp"
+#include "ldpc_family.hpp"
+#include "ldpc_family_blocks.hpp"
 #include "ofdm.hpp"
 #include "ofdm_blocks.hpp"
 #include "osc.hpp"
@@ -106,6 +110,10 @@ static_assert(ORION_FEC_K5 == orion::fec::kK5 && ORION_FEC_DVB_K7 == orion::fec:
 static_assert(ORION_LDPC_N == orion::ldpc::kN && ORION_LDPC_RULE_SUM_PRODUCT == orion::ldpc::kRuleSumProduct &&
                   ORION_LDPC_DECODED == orion::ldpc::kDecoded && ORION_COSTAS_FT4 == orion::ldpc::kFt4,
               "the header's constants are ldpc.hpp's");
+static_assert(ORION_LDPCF_N512R12 == orion::ldpcf::kN512R12 && ORION_LDPCF_N512R34 == orion::ldpcf::kN512R34 &&
+                  ORION_LDPCF_SUM_PRODUCT == orion::ldpcf::kRuleSumProduct &&
+                  ORION_LDPCF_SCALED_MIN_SUM == orion::ldpcf::kRuleScaledMinSum,
+              "the header's constants are ldpc_family.hpp's");
 
 namespace {
 thread_local std::string g_err;
@@ -2232,6 +2240,172 @@ int orion_rs_forney_interleave_batch_device(size_t branches, size_t depth, const
   return guarded([&] {
     orion::forney_interleave_batch(branches, depth, in, nstreams, len, bits != 0, out,
                                    static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+
+/* ---- the frame chain's codes (ldpc_family.hpp, bch.hpp, k_ldpc_family.hip, k_bch.hip) ---- */
+int orion_ldpcf_dims(int code, uint32_t* out) {
+  if (!out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::ldpcf::Ldpc& c = orion::ldpcf::Ldpc::get(code);
+    const size_t v[6] = {c.n(), c.k(), c.m(), c.n_edges(), c.max_check_degree(), c.relaxed_picks()};
+    for (int i = 0; i < 6; ++i) out[i] = static_cast<uint32_t>(v[i]);
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_graph(int code, uint32_t* check_start, uint32_t* check_bits, uint32_t* bit_start,
+                      uint32_t* bit_checks, uint32_t* bit_edges) {
+  if (!check_start || !check_bits || !bit_start || !bit_checks || !bit_edges) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::ldpcf::Ldpc& c = orion::ldpcf::Ldpc::get(code);
+    std::copy(c.check_start().begin(), c.check_start().end(), check_start);
+    std::copy(c.check_bits().begin(), c.check_bits().end(), check_bits);
+    std::copy(c.bit_start().begin(), c.bit_start().end(), bit_start);
+    std::copy(c.bit_checks().begin(), c.bit_checks().end(), bit_checks);
+    std::copy(c.bit_edges().begin(), c.bit_edges().end(), bit_edges);
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_encode(int code, const uint8_t* msgs, size_t nwords, uint8_t* cws) {
+  if (nwords && (!msgs || !cws)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "ldpc family: nwords above 2^32");
+  return guarded([&] {
+    const orion::ldpcf::Ldpc& c = orion::ldpcf::Ldpc::get(code);
+    for (size_t w = 0; w < nwords; ++w) c.encode(msgs + w * c.k(), cws + w * c.n());
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_syndrome_weight(int code, const uint8_t* hard, size_t nwords, int32_t* unsat) {
+  if (nwords && (!hard || !unsat)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "ldpc family: nwords above 2^32");
+  return guarded([&] {
+    const orion::ldpcf::Ldpc& c = orion::ldpcf::Ldpc::get(code);
+    for (size_t w = 0; w < nwords; ++w) unsat[w] = static_cast<int32_t>(c.syndrome_weight(hard + w * c.n()));
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_decode_soft(int code, const float* llr, size_t nwords, size_t max_iter, int rule, float scale,
+                            uint8_t* bits, int32_t* unsat, int32_t* iterations) {
+  if (nwords && (!llr || !bits || !unsat || !iterations)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "ldpc family: nwords above 2^32");
+  return guarded([&] {
+    const orion::ldpcf::Ldpc& c = orion::ldpcf::Ldpc::get(code);
+    orion::ldpcf::check_rule(rule);
+    if (max_iter > orion::kLdpcfMaxIter) throw std::invalid_argument("ldpc family decode: max_iter above 2^30");
+    for (size_t w = 0; w < nwords; ++w) {
+      const orion::ldpcf::DecodeResult r = c.decode_soft(llr + w * c.n(), max_iter, rule, scale, bits + w * c.k());
+      unsat[w] = static_cast<int32_t>(r.unsat);
+      iterations[w] = static_cast<int32_t>(r.iterations);
+    }
+    return ORION_OK;
+  });
+}
+size_t orion_ldpcf_decode_blocks(int code, size_t n_llr, size_t rows, size_t cols) {
+  return size_or_zero([&] { return orion::ldpcf_decode_blocks(code, n_llr, rows, cols); });
+}
+int orion_ldpcf_decode_batch(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows, size_t cols,
+                             size_t max_iter, int rule, float scale, uint8_t* bits, int32_t* unsat,
+                             int32_t* iterations) {
+  if (nstreams && (!llr || !bits || !unsat || !iterations)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpcf_decode_batch_host(code, llr, nstreams, n_llr, rows, cols, max_iter, rule, scale, bits, unsat,
+                                   iterations);
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_decode_batch_device(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows,
+                                    size_t cols, size_t max_iter, int rule, float scale, uint8_t* bits,
+                                    int32_t* unsat, int32_t* iterations, void* stream) {
+  if (nstreams && (!llr || !bits || !unsat || !iterations)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpcf_decode_batch(code, llr, nstreams, n_llr, rows, cols, max_iter, rule, scale, bits, unsat, iterations,
+                              static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_ldpcf_encoded_len(int code, size_t nbits, size_t rows, size_t cols) {
+  return size_or_zero([&] { return orion::ldpcf_encoded_len(code, nbits, rows, cols); });
+}
+int orion_ldpcf_encode_batch(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows, size_t cols,
+                             uint8_t* coded) {
+  if (nstreams && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpcf_encode_batch_host(code, bits, nstreams, nbits, rows, cols, coded);
+    return ORION_OK;
+  });
+}
+int orion_ldpcf_encode_batch_device(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows,
+                                    size_t cols, uint8_t* coded, void* stream) {
+  if (nstreams && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::ldpcf_encode_batch(code, bits, nstreams, nbits, rows, cols, coded, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+size_t orion_bch_parity_bits(size_t t) {
+  return size_or_zero([&] { return orion::bch::Bch(255, t).parity_bits(); });
+}
+int orion_bch_generator(size_t n, size_t t, uint8_t* out) {
+  if (!out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::bch::Bch code(n, t);
+    std::memcpy(out, code.generator().data(), code.generator().size());
+    return ORION_OK;
+  });
+}
+int orion_bch_encode(size_t n, size_t t, const uint8_t* msgs, size_t nwords, uint8_t* cws) {
+  if (nwords && (!msgs || !cws)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "bch: nwords above 2^32");
+  return guarded([&] {
+    const orion::bch::Bch code(n, t);
+    for (size_t w = 0; w < nwords; ++w) code.encode(msgs + w * code.k(), cws + w * n);
+    return ORION_OK;
+  });
+}
+int orion_bch_decode(size_t n, size_t t, const uint8_t* words, size_t nwords, uint8_t* msgs, int32_t* status,
+                     int32_t* locator_len) {
+  if (nwords && (!words || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  if (nwords > kRsMaxHostWords) return fail(ORION_E_ARG, "bch: nwords above 2^32");
+  return guarded([&] {
+    const orion::bch::Bch code(n, t);
+    for (size_t w = 0; w < nwords; ++w) {
+      size_t len = 0;
+      status[w] = code.decode(words + w * n, msgs + w * code.k(), &len);
+      if (locator_len) locator_len[w] = static_cast<int32_t>(len);
+    }
+    return ORION_OK;
+  });
+}
+int orion_bch_decode_batch(size_t t, size_t info_bits, const uint8_t* in, size_t nstreams, size_t nb, uint8_t* msgs,
+                           int32_t* status) {
+  if (nstreams && (!in || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::bch_decode_batch_host(t, info_bits, in, nstreams, nb, msgs, status);
+    return ORION_OK;
+  });
+}
+int orion_bch_decode_batch_device(size_t t, size_t info_bits, const uint8_t* in, size_t nstreams, size_t nb,
+                                  uint8_t* msgs, int32_t* status, void* stream) {
+  if (nstreams && (!in || !msgs || !status)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::bch_decode_batch(t, info_bits, in, nstreams, nb, msgs, status, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_bch_encode_batch(size_t t, size_t info_bits, const uint8_t* bits, size_t nstreams, size_t nbits,
+                           uint8_t* coded) {
+  if (nstreams && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::bch_encode_batch_host(t, info_bits, bits, nstreams, nbits, coded);
+    return ORION_OK;
+  });
+}
+int orion_bch_encode_batch_device(size_t t, size_t info_bits, const uint8_t* bits, size_t nstreams, size_t nbits,
+                                  uint8_t* coded, void* stream) {
+  if (nstreams && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::bch_encode_batch(t, info_bits, bits, nstreams, nbits, coded, static_cast<hipStream_t>(stream));
     return ORION_OK;
   });
 }

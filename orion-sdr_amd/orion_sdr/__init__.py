@@ -3794,3 +3794,330 @@ def forney_interleave_batch(x, branches, depth, bits=False, stream=None):
         _arg_check(_L.orion_rs_forney_interleave_batch(I, M, a.ctypes.data, ns, length, int(bool(bits)),
                                                        out.ctypes.data))
     return out
+
+
+# ---- the frame chain's codes: the constructed LDPC family and the shortened BCH code
+# (src/fec/ldpc_codes.rs, src/fec/bch.rs) ----
+def _fec2_sigs():
+    vp, sz, i, f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+    sig = {
+        "orion_ldpcf_dims": (i, [i, vp]), "orion_ldpcf_graph": (i, [i, vp, vp, vp, vp, vp]),
+        "orion_ldpcf_encode": (i, [i, vp, sz, vp]), "orion_ldpcf_syndrome_weight": (i, [i, vp, sz, vp]),
+        "orion_ldpcf_decode_soft": (i, [i, vp, sz, sz, i, f, vp, vp, vp]),
+        "orion_ldpcf_decode_blocks": (sz, [i, sz, sz, sz]),
+        "orion_ldpcf_decode_batch": (i, [i, vp, sz, sz, sz, sz, sz, i, f, vp, vp, vp]),
+        "orion_ldpcf_decode_batch_device": (i, [i, vp, sz, sz, sz, sz, sz, i, f, vp, vp, vp, vp]),
+        "orion_ldpcf_encoded_len": (sz, [i, sz, sz, sz]),
+        "orion_ldpcf_encode_batch": (i, [i, vp, sz, sz, sz, sz, vp]),
+        "orion_ldpcf_encode_batch_device": (i, [i, vp, sz, sz, sz, sz, vp, vp]),
+        "orion_bch_parity_bits": (sz, [sz]), "orion_bch_generator": (i, [sz, sz, vp]),
+        "orion_bch_encode": (i, [sz, sz, vp, sz, vp]), "orion_bch_decode": (i, [sz, sz, vp, sz, vp, vp, vp]),
+        "orion_bch_decode_batch": (i, [sz, sz, vp, sz, sz, vp, vp]),
+        "orion_bch_decode_batch_device": (i, [sz, sz, vp, sz, sz, vp, vp, vp]),
+        "orion_bch_encode_batch": (i, [sz, sz, vp, sz, sz, vp]),
+        "orion_bch_encode_batch_device": (i, [sz, sz, vp, sz, sz, vp, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_fec2_sigs()
+
+LDPC_CODES = {"n512r12": 0, "n576r23": 1, "n512r34": 2}  # ldpc_codes.rs:46-73
+LDPC_RULES = {"sum_product": 0, "min_sum": 1, "scaled_min_sum": 2}  # ldpc_codes.rs:97-105
+BCH_INFO_BITS = 120  # modulate/ofdm_frame.rs:485
+__all__ += ["LDPC_CODES", "LDPC_RULES", "BCH_INFO_BITS", "Ldpc", "Bch", "BchUncorrectable", "ldpc_family_encode_batch",
+            "ldpc_family_decode_batch", "bch_encode_batch", "bch_decode_batch"]
+
+
+def _ldpcf_code(code) -> int:
+    if isinstance(code, Ldpc):
+        return code.index
+    if not isinstance(code, str) or code not in LDPC_CODES:
+        raise ValueError(f"code: one of {sorted(LDPC_CODES)}")
+    return LDPC_CODES[code]
+
+
+def _ldpcf_rule(rule):
+    """"sum_product", "min_sum" or ("scaled_min_sum", a) -> (rule index, scale)."""
+    if isinstance(rule, str) and rule in ("sum_product", "min_sum"):
+        return LDPC_RULES[rule], 1.0
+    if isinstance(rule, (tuple, list)) and len(rule) == 2 and rule[0] == "scaled_min_sum":
+        try:
+            return LDPC_RULES["scaled_min_sum"], float(np.float32(rule[1]))
+        except (TypeError, ValueError):
+            pass
+    raise ValueError('rule: "sum_product", "min_sum" or ("scaled_min_sum", a)')
+
+
+def _ldpcf_max_iter(max_iter) -> int:
+    max_iter = int(max_iter)
+    if max_iter < 0 or max_iter > 1 << 30:
+        raise ValueError("max_iter: 0 to 2^30")
+    return max_iter
+
+
+class Ldpc:
+    """Ldpc (fec/ldpc_codes.rs), host only: one of the three constructed codes "n512r12" (N =
+    512, K = 256), "n576r23" (576, 384), "n512r34" (512, 384). The library builds a code on
+    first use and keeps it. LLRs are positive for bit 0."""
+
+    def __init__(self, code):
+        self.index = _ldpcf_code(code)
+        self.code = code.code if isinstance(code, Ldpc) else code
+        d = np.zeros(6, np.uint32)
+        _arg_check(_L.orion_ldpcf_dims(self.index, d.ctypes.data))
+        self.n, self.k, self.m, self.n_edges, self.max_check_degree, self.relaxed_picks = (int(v) for v in d)
+
+    def graph(self):
+        """The Tanner graph as CSR, uint32: check_start (M + 1,), check_bits (edges,) (within a
+        check the message columns ascending, then K + i, then K + i - 1), bit_start (N + 1,),
+        bit_checks (edges,) (ascending) and bit_edges (edges,), the index into check_bits of
+        that bit in that check."""
+        g = {"check_start": np.zeros(self.m + 1, np.uint32), "check_bits": np.zeros(self.n_edges, np.uint32),
+             "bit_start": np.zeros(self.n + 1, np.uint32), "bit_checks": np.zeros(self.n_edges, np.uint32),
+             "bit_edges": np.zeros(self.n_edges, np.uint32)}
+        _arg_check(_L.orion_ldpcf_graph(self.index, *(a.ctypes.data for a in g.values())))
+        return g
+
+    @staticmethod
+    def _words(x, width, dtype, what):
+        if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim not in (1, 2) or x.shape[-1] != width:
+            raise ValueError(f"{what}: expected {np.dtype(dtype).name} ({width},) or (nwords, {width})")
+        return np.ascontiguousarray(x), x.ndim == 1
+
+    def encode(self, message) -> np.ndarray:
+        """message (K,) or (nwords, K) uint8 -> codeword(s) message | parity (N)."""
+        m, _ = self._words(message, self.k, np.uint8, "message")
+        out = np.zeros(m.shape[:-1] + (self.n,), np.uint8)
+        _arg_check(_L.orion_ldpcf_encode(self.index, m.ctypes.data, m.size // self.k, out.ctypes.data))
+        return out
+
+    def syndrome_weight(self, hard):
+        """Unsatisfied checks of hard (N,) -> int, or (nwords, N) -> int32 (nwords,)."""
+        h, one = self._words(hard, self.n, np.uint8, "hard")
+        out = np.zeros(h.size // self.n, np.int32)
+        _arg_check(_L.orion_ldpcf_syndrome_weight(self.index, h.ctypes.data, out.size, out.ctypes.data))
+        return int(out[0]) if one else out
+
+    def decode_soft(self, llr, max_iter=50, rule="sum_product"):
+        """decode_soft_with (ldpc_codes.rs:366-540): float32 llr (N,) -> (bits (K,), unsat,
+        iterations), or (nwords, N) -> (bits (nwords, K), unsat, iterations int32 (nwords,)).
+        unsat is the smallest unsatisfied-check count seen (0: decoded), iterations the
+        iterations run (0: the initial decision was a codeword). rule: "sum_product",
+        "min_sum" or ("scaled_min_sum", a)."""
+        r, scale = _ldpcf_rule(rule)
+        l, one = self._words(llr, self.n, np.float32, "llr")
+        nw = l.size // self.n
+        bits = np.zeros(l.shape[:-1] + (self.k,), np.uint8)
+        unsat, iters = np.zeros(nw, np.int32), np.zeros(nw, np.int32)
+        _arg_check(_L.orion_ldpcf_decode_soft(self.index, l.ctypes.data, nw, _ldpcf_max_iter(max_iter), r, scale,
+                                              bits.ctypes.data, unsat.ctypes.data, iters.ctypes.data))
+        return (bits, int(unsat[0]), int(iters[0])) if one else (bits, unsat, iters)
+
+
+class BchUncorrectable(ValueError):
+    """Bch.decode of an uncorrectable word; message is the systematic prefix received[:k],
+    errors the reference's payload max(residual syndromes, roots found)."""
+
+    def __init__(self, message, errors):
+        super().__init__(f"codeword has {errors} residual errors after decoding (uncorrectable)")
+        self.message = message
+        self.errors = errors
+
+
+class Bch:
+    """Bch (fec/bch.rs), host only: the binary BCH code over GF(2^8) correcting t bit errors,
+    shortened to n elements (1 <= n <= 255, parity bits < n) of one bit each, index 0 the
+    highest degree. An element is set when it is nonzero; a correction is ^= 1."""
+
+    def __init__(self, t, n=255):
+        t, n = int(t), int(n)
+        if t < 1:
+            raise ValueError("bch: design t = 0")
+        pb = int(_L.orion_bch_parity_bits(t)) if t <= 1 << 16 else 0
+        if pb == 0:
+            raise ValueError("bch: design t is too large for GF(2^8) (parity would exceed the block)")
+        if n < 1 or n > 255 or pb >= n:
+            raise ValueError("bch: shortened length n is out of range 1..=255 or leaves no room for parity")
+        self.t, self.n, self.parity_bits, self.k = t, n, pb, n - pb
+
+    @classmethod
+    def for_info_bits(cls, t, info_bits=BCH_INFO_BITS):
+        """shortened_bch_for (modulate/ofdm_frame.rs:547-552): the code of t whose message is
+        info_bits long; the frame's is t = 8 over 120 bits, n = 184."""
+        info_bits = int(info_bits)
+        if info_bits < 1:
+            raise ValueError("info_bits: at least 1")
+        return cls(t, info_bits + cls(t).parity_bits)
+
+    def generator(self) -> np.ndarray:
+        """g(x), highest degree first, 0 / 1: parity_bits + 1 coefficients."""
+        out = np.zeros(self.parity_bits + 1, np.uint8)
+        _arg_check(_L.orion_bch_generator(self.n, self.t, out.ctypes.data))
+        return out
+
+    def _words(self, x, width, what):
+        if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.ndim not in (1, 2) or x.shape[-1] != width:
+            raise ValueError(f"{what}: expected uint8 ({width},) or (nwords, {width})")
+        return np.ascontiguousarray(x), x.ndim == 1
+
+    def encode(self, message) -> np.ndarray:
+        """message (k,) or (nwords, k) -> codeword(s) message | parity."""
+        m, _ = self._words(message, self.k, "message")
+        out = np.zeros(m.shape[:-1] + (self.n,), np.uint8)
+        _arg_check(_L.orion_bch_encode(self.n, self.t, m.ctypes.data, m.size // self.k, out.ctypes.data))
+        return out
+
+    def decode_counted(self, received, locator_len=False):
+        """decode (bch.rs:131-207) with its outcome as a number: received (n,) -> (message (k,),
+        status), or (nwords, n) -> (messages (nwords, k), status int32 (nwords,)). status is the
+        number of bits flipped, parity included, or -max(residual syndromes, roots found) <= -1
+        for an uncorrectable word, whose message is received[:k]. locator_len: also the
+        entries of the Berlekamp-Massey locator vector (0 for a clean word)."""
+        r, one = self._words(received, self.n, "received")
+        msgs = np.zeros(r.shape[:-1] + (self.k,), np.uint8)
+        status, loc = np.zeros(r.size // self.n, np.int32), np.zeros(r.size // self.n, np.int32)
+        _arg_check(_L.orion_bch_decode(self.n, self.t, r.ctypes.data, status.size, msgs.ctypes.data, status.ctypes.data,
+                                       loc.ctypes.data))
+        out = (msgs, int(status[0])) if one else (msgs, status)
+        return out + ((int(loc[0]) if one else loc),) if locator_len else out
+
+    def decode(self, received) -> np.ndarray:
+        """decode of one word; raises BchUncorrectable (carrying received[:k]) where the
+        reference returns Uncorrectable."""
+        if not isinstance(received, np.ndarray) or received.ndim != 1:
+            raise ValueError(f"received: expected uint8 ({self.n},)")
+        msg, status = self.decode_counted(received)
+        if status < 0:
+            raise BchUncorrectable(msg, -status)
+        return msg
+
+
+def _fec2_arg(x, what, dtype, ndims):
+    """x as a contiguous numpy array or torch CUDA tensor of dtype and one of ndims dimensions."""
+    if _is_torch(x):
+        import torch
+
+        if not x.is_cuda or not x.is_contiguous() or x.dtype != getattr(torch, dtype) or x.dim() not in ndims:
+            raise ValueError(f"{what}: a contiguous {dtype} CUDA tensor of {' or '.join(map(str, ndims))} dimensions")
+        return x, True
+    if not isinstance(x, np.ndarray) or x.dtype != getattr(np, dtype) or x.ndim not in ndims:
+        raise ValueError(f"{what}: expected a {dtype} array of {' or '.join(map(str, ndims))} dimensions")
+    return np.ascontiguousarray(x), False
+
+
+def ldpc_family_encode_batch(bits, code, interleaver=None, stream=None):
+    """LDPC encode and (with interleaver, a BlockInterleaver or (rows, cols)) block interleave a
+    batch of streams on the GPU in one launch: uint8 (nstreams, nbits) -> uint8 (nstreams, coded
+    length): ceil(nbits / K) codewords of code ("n512r12", "n576r23", "n512r34"), the last
+    message zero-padded, rounded up to whole interleaver blocks (zero padding). Row k is
+    interleave_bits of the Ldpc(code).encode of its K-bit blocks. A numpy array (-> numpy) or a
+    contiguous torch CUDA tensor (-> a torch tensor on its device, queued on torch's current
+    stream or on stream)."""
+    c = _ldpcf_code(code)
+    rows, cols = _fec_il(interleaver)
+    b, dev = _fec2_arg(bits, "bits", "uint8", (2,))
+    ns, nbits = int(b.shape[0]), int(b.shape[1])
+    if nbits < 1:
+        raise ValueError("bits: at least one bit per stream")
+    out_len = int(_L.orion_ldpcf_encoded_len(c, nbits, rows, cols))
+    if out_len == 0:
+        raise ValueError(_err())
+    out = _rs_out(b, dev, (ns, out_len), "uint8")
+    if dev:
+        _arg_check(_L.orion_ldpcf_encode_batch_device(c, b.data_ptr(), ns, nbits, rows, cols, out.data_ptr(),
+                                                      SyncEngine._stream(b, stream)))
+    else:
+        _arg_check(_L.orion_ldpcf_encode_batch(c, b.ctypes.data, ns, nbits, rows, cols, out.ctypes.data))
+    return out
+
+
+def ldpc_family_decode_batch(llr, code, max_iter=50, rule="sum_product", interleaver=None, stream=None):
+    """Belief-propagation decode of a batch of streams on the GPU in one launch, one wave per
+    codeword, the block deinterleaver fused into the LLR fetch: float32 (nstreams, n_llr),
+    positive meaning bit 0 -> (bits uint8 (nstreams, nblocks * K), unsat int32 (nstreams,
+    nblocks), iterations int32 (nstreams, nblocks)), nblocks = n_llr // N. Codeword LLR j of a
+    stream is element j of deinterleave_llrs(llr[k]) (n_llr must then be whole interleaver
+    blocks); what lies past nblocks * N is padding and is not read. Every word equals
+    Ldpc(code).decode_soft(word, max_iter, rule) in all three outputs. rule: "sum_product",
+    "min_sum" or ("scaled_min_sum", a). A numpy array (-> numpy) or a contiguous torch CUDA
+    tensor, such as the llr of ofdm_demodulate_batch(..., llr=True) (-> torch tensors on its
+    device, queued on torch's current stream or on stream)."""
+    c = _ldpcf_code(code)
+    r, scale = _ldpcf_rule(rule)
+    mi = _ldpcf_max_iter(max_iter)
+    rows, cols = _fec_il(interleaver)
+    l, dev = _fec2_arg(llr, "llr", "float32", (2,))
+    ns, nl = int(l.shape[0]), int(l.shape[1])
+    nblocks = int(_L.orion_ldpcf_decode_blocks(c, nl, rows, cols))
+    if nblocks == 0:
+        raise ValueError(_err())
+    k = (256, 384, 384)[c]
+    bits, unsat, iters = (_rs_out(l, dev, (ns, nblocks * k), "uint8"), _rs_out(l, dev, (ns, nblocks), "int32"),
+                          _rs_out(l, dev, (ns, nblocks), "int32"))
+    args = (c, _rs_ptr(l, dev), ns, nl, rows, cols, mi, r, scale, _rs_ptr(bits, dev), _rs_ptr(unsat, dev),
+            _rs_ptr(iters, dev))
+    if dev:
+        _arg_check(_L.orion_ldpcf_decode_batch_device(*args, SyncEngine._stream(l, stream)))
+    else:
+        _arg_check(_L.orion_ldpcf_decode_batch(*args))
+    return bits, unsat, iters
+
+
+def _bch_device_code(t, info_bits):
+    t = int(t)
+    if t < 1 or t > 31:
+        raise ValueError("bch: 1 <= t <= 31 on the device")
+    return Bch.for_info_bits(t, info_bits)
+
+
+def bch_encode_batch(bits, t, info_bits=BCH_INFO_BITS, stream=None):
+    """BCH encode a batch of streams on the GPU in one launch, one wave per word: uint8
+    (nstreams, nbits) or (nbits,) -> (..., ncw * n), ncw = ceil(nbits / info_bits) words of
+    Bch.for_info_bits(t, info_bits), the last message zero-padded (outer_encode,
+    modulate/ofdm_frame.rs:495-505). 1 <= t <= 31. A numpy array (-> numpy) or a contiguous
+    torch CUDA tensor (-> a torch tensor on its device, queued on torch's current stream or on
+    stream)."""
+    code = _bch_device_code(t, info_bits)
+    b, dev = _fec2_arg(bits, "bits", "uint8", (1, 2))
+    batched = len(b.shape) == 2
+    ns, nbits = (int(b.shape[0]), int(b.shape[1])) if batched else (1, int(b.shape[0]))
+    if nbits < 1:
+        raise ValueError("bits: at least one bit per stream")
+    out_len = -(-nbits // code.k) * code.n
+    out = _rs_out(b, dev, (ns, out_len) if batched else (out_len,), "uint8")
+    if dev:
+        _arg_check(_L.orion_bch_encode_batch_device(code.t, code.k, b.data_ptr(), ns, nbits, out.data_ptr(),
+                                                    SyncEngine._stream(b, stream)))
+    else:
+        _arg_check(_L.orion_bch_encode_batch(code.t, code.k, b.ctypes.data, ns, nbits, out.ctypes.data))
+    return out
+
+
+def bch_decode_batch(bits, t, info_bits=BCH_INFO_BITS, stream=None):
+    """BCH decode a batch of streams on the GPU in one launch, one wave per word: uint8
+    (nstreams, nb) or (nb,), one bit per element as ldpc_family_decode_batch or
+    conv_viterbi_batch write them -> (bits (..., ncw * info_bits), status int32 (..., ncw)), ncw
+    = nb // n words of Bch.for_info_bits(t, info_bits) per stream, the tail ignored. Both equal
+    Bch.decode_counted of every word: status is the number of bits flipped, or negative for an
+    uncorrectable word, whose message is received[:k]. 1 <= t <= 31. A numpy array (-> numpy)
+    or a contiguous torch CUDA tensor (-> torch tensors on its device, queued on torch's
+    current stream or on stream)."""
+    code = _bch_device_code(t, info_bits)
+    b, dev = _fec2_arg(bits, "bits", "uint8", (1, 2))
+    batched = len(b.shape) == 2
+    ns, nb = (int(b.shape[0]), int(b.shape[1])) if batched else (1, int(b.shape[0]))
+    ncw = nb // code.n
+    if ncw < 1:
+        raise ValueError(f"bits: a stream is at least one codeword of n = {code.n} bits")
+    msgs = _rs_out(b, dev, (ns, ncw * code.k) if batched else (ncw * code.k,), "uint8")
+    status = _rs_out(b, dev, (ns, ncw) if batched else (ncw,), "int32")
+    args = (code.t, code.k, _rs_ptr(b, dev), ns, nb, _rs_ptr(msgs, dev), _rs_ptr(status, dev))
+    if dev:
+        _arg_check(_L.orion_bch_decode_batch_device(*args, SyncEngine._stream(b, stream)))
+    else:
+        _arg_check(_L.orion_bch_decode_batch(*args))
+    return msgs, status
