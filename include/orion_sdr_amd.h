@@ -1232,6 +1232,130 @@ int orion_bch_encode_batch(size_t t, size_t info_bits, const uint8_t* bits, size
 int orion_bch_encode_batch_device(size_t t, size_t info_bits, const uint8_t* bits, size_t nstreams, size_t nbits,
                                   uint8_t* coded, void* stream);
 
+/* ---- the coding chain of the COFDM frame layer (modulate/ofdm_frame.rs:204-682,
+ * demodulate/ofdm_frame.rs:351-779, codec/crc.rs:89-130, fec/frame.rs) ----
+ *   payload -> CRC -> [scramble] -> outer FEC -> outer interleave -> inner FEC ->
+ *              inner interleave -> [scramble] -> coded bits            (reversed on receive)
+ * Bits are one per byte, MSB first within a byte. */
+#define ORION_FRAME_CRC_NONE 0
+#define ORION_FRAME_CRC16 1 /* CCITT-FALSE */
+#define ORION_FRAME_CRC32 2 /* ISO-HDLC */
+#define ORION_FRAME_OUTER_NONE 0
+#define ORION_FRAME_OUTER_BCH 1 /* a = t, over 120 information bits */
+#define ORION_FRAME_OUTER_RS 2  /* a = n, b = n_parity */
+#define ORION_FRAME_INNER_NONE 0
+#define ORION_FRAME_INNER_LDPC 1 /* a = the orion_ldpcf code */
+#define ORION_FRAME_INNER_CONV 2 /* a = ORION_FEC_K5 / ORION_FEC_DVB_K7, b = ORION_FEC_RATE_* */
+#define ORION_FRAME_IL_NONE 0
+#define ORION_FRAME_IL_BLOCK 1  /* a = rows, b = cols */
+#define ORION_FRAME_IL_FORNEY 2 /* a = branches, b = depth (frame mode) */
+#define ORION_FRAME_SCR_NONE 0
+#define ORION_FRAME_SCR_ADDITIVE 1
+#define ORION_FRAME_SCR_DVBT 2 /* DVB-T energy dispersal: before the outer code only */
+#define ORION_FRAME_SCR_BEFORE_OUTER 0
+#define ORION_FRAME_SCR_AFTER_INNER 1
+#define ORION_FRAME_HEADER_FIELD_BYTES 14
+/* RxError, fec/frame.rs:59-77; 0 is no error */
+#define ORION_RX_PREAMBLE_TIMEOUT 1
+#define ORION_RX_MALFORMED_HEADER 2
+#define ORION_RX_HEADER_CRC_MISMATCH 3
+#define ORION_RX_CRC_MISMATCH 4
+#define ORION_RX_FEC_UNCORRECTABLE 5
+typedef struct {
+  int32_t crc;
+  int32_t outer;
+  uint32_t outer_a, outer_b;
+  int32_t inner;
+  uint32_t inner_a, inner_b;
+  int32_t outer_il;
+  uint32_t outer_il_a, outer_il_b;
+  int32_t inner_il;
+  uint32_t inner_il_a, inner_il_b;
+  int32_t scrambler;
+  uint32_t scr_poly, scr_width;
+  int32_t scr_per_frame; /* SeedMode::PerFrameRandom: the seed is the call's, not scr_seed */
+  uint32_t scr_seed;     /* SeedMode::Fixed */
+  int32_t scrambler_pos;
+} orion_frame_scheme;
+uint32_t orion_frame_crc16(const uint8_t* data, size_t n);
+uint32_t orion_frame_crc32(const uint8_t* data, size_t n);
+/* out [n + 0 | 2 | 4] = data | crc, big-endian */
+int orion_frame_append_crc(int crc, const uint8_t* data, size_t n, uint8_t* out);
+/* data = payload | crc: *ok = 1 when it checks. ORION_E_ARG when n is shorter than the CRC. */
+int orion_frame_check_crc(int crc, const uint8_t* data, size_t n, int32_t* ok);
+/* fields [5]: mcs_index, payload_len, sequence_num, flags, scrambler_seed <-> the 14 bytes */
+int orion_frame_pack_header(const uint32_t* fields, uint8_t* out14);
+int orion_frame_unpack_header(const uint8_t* in14, uint32_t* fields);
+/* build_scrambler's seed: raw reduced to width bits (all 32 when width >= 32), 0 mapped to 1 */
+uint32_t orion_frame_reduce_seed(uint32_t width, uint32_t raw);
+/* scramble_bytes / scramble_bits / apply_pn_to_llrs of the scheme's scrambler, in place,
+ * whatever its position. Bit i meets PN step 8 (i / 8) + 7 - i % 8. */
+int orion_frame_scramble_bytes(const orion_frame_scheme* s, uint32_t per_frame_seed, uint8_t* bytes, size_t n);
+int orion_frame_scramble_bits(const orion_frame_scheme* s, uint32_t per_frame_seed, uint8_t* bits, size_t n);
+int orion_frame_apply_pn_to_llrs(const orion_frame_scheme* s, uint32_t per_frame_seed, float* llr, size_t n);
+/* plan [6]: info_bytes, framed_bytes, outer_coded_bits, outer_il_bits, inner_coded_bits, coded_bits */
+int orion_frame_block_plan(const orion_frame_scheme* s, size_t info_bytes, size_t* plan);
+/* encode_chain_stages: coded [plan.coded_bits], outer_il_bits [plan.outer_il_bits] (may be NULL) */
+int orion_frame_encode_chain(const orion_frame_scheme* s, const uint8_t* bytes, size_t n, uint32_t per_frame_seed,
+                             uint8_t* coded, uint8_t* outer_il_bits);
+/* decode_chain under block_plan(info_bytes): bytes [info_bytes]; outcome [8] = the RxError (0,
+ * or ORION_RX_MALFORMED_HEADER and nothing else is written), inner_ok, outer_ok, crc_ok,
+ * crc_present, outer_present, outer_corrected_bytes (-1: none reported), is_valid;
+ * inner_out_bits [inner_cap] (may be NULL) takes the untrimmed inner decoder output,
+ * *inner_out_len its length (ORION_E_ARG when it does not fit). LDPC runs 50 iterations. */
+int orion_frame_decode_chain(const orion_frame_scheme* s, const float* llr, size_t n_llr, size_t info_bytes,
+                             uint32_t per_frame_seed, int ldpc_rule, float ldpc_scale, uint8_t* bytes,
+                             int32_t* outcome, uint8_t* inner_out_bits, size_t inner_cap, size_t* inner_out_len);
+/* The glue kernels between the batched codes, one wave per frame (k_frame.hip). Host slices
+ * (synchronous) or device buffers on a stream. seeds [nframes] i64 (per-frame seeds) or NULL
+ * for the scheme's fixed seed. nframes <= 2^24, info_len <= 2^16, rows <= 2^24 elements.
+ * pack: payload [nframes][info_len], or fields [nframes][5] i64 for a header (info_len 14)
+ * -> out [nframes][framed * 8] bits or (out_bytes) [nframes][framed] bytes: append_crc, then
+ * scramble_bytes when the scrambler sits before the outer code.
+ * unpack: the first framed * 8 bits (or, in_bytes, framed bytes) of each row of in
+ * [nframes][in_stride]; unsat [nframes][n_inner] and status [nframes][n_outer] i32 (either may
+ * be NULL) are the decoders' per-word outputs -> payload [nframes][info_len], flags
+ * [nframes][4] = inner_ok, outer_ok, crc_ok, is_valid, corrected [nframes] i32 (the sum of
+ * the non-negative status entries), fields [nframes][5] i64 (header; else NULL).
+ * coded_bits: out [nframes][out_len] = the first nbits of in [nframes][in_stride],
+ * scramble_bits applied when the Additive scrambler sits after the inner code, then zeros.
+ * llr_prepare: out [nframes][n] = the first n LLRs of in [nframes][in_stride],
+ * apply_pn_to_llrs applied under the same condition. */
+int orion_frame_pack_batch(const orion_frame_scheme* s, const uint8_t* payload, const int64_t* fields,
+                           const int64_t* seeds, size_t nframes, size_t info_len, int out_bytes, uint8_t* out);
+int orion_frame_pack_batch_device(const orion_frame_scheme* s, const uint8_t* payload, const int64_t* fields,
+                                  const int64_t* seeds, size_t nframes, size_t info_len, int out_bytes, uint8_t* out,
+                                  void* stream);
+int orion_frame_unpack_batch(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, int in_bytes,
+                             const int64_t* seeds, const int32_t* unsat, size_t n_inner, const int32_t* status,
+                             size_t n_outer, size_t nframes, size_t info_len, uint8_t* payload, uint8_t* flags,
+                             int32_t* corrected, int64_t* fields);
+int orion_frame_unpack_batch_device(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, int in_bytes,
+                                    const int64_t* seeds, const int32_t* unsat, size_t n_inner,
+                                    const int32_t* status, size_t n_outer, size_t nframes, size_t info_len,
+                                    uint8_t* payload, uint8_t* flags, int32_t* corrected, int64_t* fields,
+                                    void* stream);
+int orion_frame_coded_bits_batch(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, size_t nbits,
+                                 const int64_t* seeds, size_t nframes, size_t out_len, uint8_t* out);
+int orion_frame_coded_bits_batch_device(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride,
+                                        size_t nbits, const int64_t* seeds, size_t nframes, size_t out_len,
+                                        uint8_t* out, void* stream);
+int orion_frame_llr_prepare_batch(const orion_frame_scheme* s, const float* in, size_t in_stride, size_t n,
+                                  const int64_t* seeds, size_t nframes, float* out);
+int orion_frame_llr_prepare_batch_device(const orion_frame_scheme* s, const float* in, size_t in_stride, size_t n,
+                                         const int64_t* seeds, size_t nframes, float* out, void* stream);
+/* The frames' IQ on the device (cf32): out [nframes][lead_len + hdr_len + pay_len] = the shared
+ * lead (S&C repeats and training symbol), then each frame's header and payload symbols. With
+ * ramp [ramp_len] f32 (SymbolWindow's ramp, 2 ramp_len <= sps; NULL / 0 for none) every whole
+ * symbol of sps samples from win_start on is tapered, the frame modulator's window post-pass. */
+int orion_frame_assemble_batch_device(const void* lead, size_t lead_len, const void* hdr, size_t hdr_len,
+                                      const void* pay, size_t pay_len, size_t nframes, size_t sps, size_t win_start,
+                                      const float* ramp, size_t ramp_len, void* out, void* stream);
+/* in [nframes][nbytes] -> out [nframes][nbytes * 8], MSB first */
+int orion_frame_bytes_to_bits_batch(const uint8_t* in, size_t nframes, size_t nbytes, uint8_t* out);
+int orion_frame_bytes_to_bits_batch_device(const uint8_t* in, size_t nframes, size_t nbytes, uint8_t* out,
+                                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@
 #include "blocks.hpp"
 #include "fec.hpp"
 #include "fec_blocks.hpp"
+#include "frame.hpp"
+#include "frame_blocks.hpp"
 #include "ldpc.hpp"
 #include "ldpc_family.hpp"
 #include "ldpc_family_blocks.hpp"
@@ -2406,6 +2408,255 @@ int orion_bch_encode_batch_device(size_t t, size_t info_bits, const uint8_t* bit
   if (nstreams && (!bits || !coded)) return fail(ORION_E_NULL, "null buffer");
   return guarded([&] {
     orion::bch_encode_batch(t, info_bits, bits, nstreams, nbits, coded, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+
+}  // extern "C"
+
+/* ---- the frame layer's coding chain (frame.hpp, k_frame.hip) ---- */
+namespace {
+static_assert(sizeof(long long) == sizeof(int64_t) && ORION_FRAME_CRC32 == orion::frame::kCrc32 &&
+                  ORION_FRAME_OUTER_RS == orion::frame::kOuterRs && ORION_FRAME_INNER_CONV == orion::frame::kInnerConv &&
+                  ORION_FRAME_IL_FORNEY == orion::frame::kIlForney && ORION_FRAME_SCR_DVBT == orion::frame::kScrDvbT &&
+                  ORION_FRAME_SCR_AFTER_INNER == orion::frame::kAfterInnerFec &&
+                  ORION_FRAME_HEADER_FIELD_BYTES == orion::frame::kHeaderFieldBytes &&
+                  ORION_RX_MALFORMED_HEADER == orion::frame::kRxMalformedHeader &&
+                  ORION_RX_FEC_UNCORRECTABLE == orion::frame::kRxFecUncorrectable,
+              "the header's frame constants are frame.hpp's");
+orion::frame::Scheme scheme_of(const orion_frame_scheme* s) {
+  if (!s) throw std::invalid_argument("frame: null scheme");
+  orion::frame::Scheme o;
+  o.crc = s->crc;
+  o.outer = s->outer;
+  o.outer_a = s->outer_a;
+  o.outer_b = s->outer_b;
+  o.inner = s->inner;
+  o.inner_a = s->inner_a;
+  o.inner_b = s->inner_b;
+  o.outer_il = s->outer_il;
+  o.outer_il_a = s->outer_il_a;
+  o.outer_il_b = s->outer_il_b;
+  o.inner_il = s->inner_il;
+  o.inner_il_a = s->inner_il_a;
+  o.inner_il_b = s->inner_il_b;
+  o.scrambler = s->scrambler;
+  o.scr_poly = s->scr_poly;
+  o.scr_width = s->scr_width;
+  o.scr_per_frame = s->scr_per_frame;
+  o.scr_seed = s->scr_seed;
+  o.scrambler_pos = s->scrambler_pos;
+  orion::frame::check_scheme(o);
+  return o;
+}
+const long long* ll(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+long long* ll(int64_t* p) { return reinterpret_cast<long long*>(p); }
+}  // namespace
+
+extern "C" {
+
+uint32_t orion_frame_crc16(const uint8_t* data, size_t n) { return data || !n ? orion::frame::crc16(data, n) : 0; }
+uint32_t orion_frame_crc32(const uint8_t* data, size_t n) { return data || !n ? orion::frame::crc32(data, n) : 0; }
+int orion_frame_append_crc(int crc, const uint8_t* data, size_t n, uint8_t* out) {
+  if ((n && !data) || !out) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<uint8_t> v = orion::frame::append_crc(crc, data, n);
+    std::copy(v.begin(), v.end(), out);
+    return ORION_OK;
+  });
+}
+int orion_frame_check_crc(int crc, const uint8_t* data, size_t n, int32_t* ok) {
+  if ((n && !data) || !ok) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    *ok = orion::frame::check_crc(crc, data, n) ? 1 : 0;
+    return ORION_OK;
+  });
+}
+int orion_frame_pack_header(const uint32_t* fields, uint8_t* out14) {
+  if (!fields || !out14) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame::pack_header_fields({fields[0], fields[1], fields[2], fields[3], fields[4]}, out14);
+    return ORION_OK;
+  });
+}
+int orion_frame_unpack_header(const uint8_t* in14, uint32_t* fields) {
+  if (!fields || !in14) return fail(ORION_E_NULL, "null buffer");
+  const orion::frame::HeaderFields f = orion::frame::unpack_header_fields(in14);
+  const uint32_t v[5] = {f.mcs_index, f.payload_len, f.sequence_num, f.flags, f.scrambler_seed};
+  std::copy(v, v + 5, fields);
+  return ORION_OK;
+}
+uint32_t orion_frame_reduce_seed(uint32_t width, uint32_t raw) { return orion::frame::reduce_seed(width, raw); }
+int orion_frame_scramble_bytes(const orion_frame_scheme* s, uint32_t per_frame_seed, uint8_t* bytes, size_t n) {
+  if (n && !bytes) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame::scramble_bytes(scheme_of(s), per_frame_seed, bytes, n);
+    return ORION_OK;
+  });
+}
+int orion_frame_scramble_bits(const orion_frame_scheme* s, uint32_t per_frame_seed, uint8_t* bits, size_t n) {
+  if (n && !bits) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame::scramble_bits(scheme_of(s), per_frame_seed, bits, n);
+    return ORION_OK;
+  });
+}
+int orion_frame_apply_pn_to_llrs(const orion_frame_scheme* s, uint32_t per_frame_seed, float* llr, size_t n) {
+  if (n && !llr) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame::apply_pn_to_llrs(scheme_of(s), per_frame_seed, llr, n);
+    return ORION_OK;
+  });
+}
+int orion_frame_block_plan(const orion_frame_scheme* s, size_t info_bytes, size_t* plan) {
+  if (!plan) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::frame::BlockPlan p = orion::frame::block_plan(info_bytes, scheme_of(s));
+    const size_t v[6] = {p.info_bytes,    p.framed_bytes,     p.outer_coded_bits,
+                         p.outer_il_bits, p.inner_coded_bits, p.coded_bits};
+    std::copy(v, v + 6, plan);
+    return ORION_OK;
+  });
+}
+int orion_frame_encode_chain(const orion_frame_scheme* s, const uint8_t* bytes, size_t n, uint32_t per_frame_seed,
+                             uint8_t* coded, uint8_t* outer_il_bits) {
+  if ((n && !bytes) || !coded) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::frame::EncodedStages st = orion::frame::encode_chain_stages(bytes, n, scheme_of(s), per_frame_seed);
+    std::copy(st.coded.begin(), st.coded.end(), coded);
+    if (outer_il_bits) std::copy(st.outer_il_bits.begin(), st.outer_il_bits.end(), outer_il_bits);
+    return ORION_OK;
+  });
+}
+int orion_frame_decode_chain(const orion_frame_scheme* s, const float* llr, size_t n_llr, size_t info_bytes,
+                             uint32_t per_frame_seed, int ldpc_rule, float ldpc_scale, uint8_t* bytes,
+                             int32_t* outcome, uint8_t* inner_out_bits, size_t inner_cap, size_t* inner_out_len) {
+  if ((n_llr && !llr) || (info_bytes && !bytes) || !outcome) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::frame::Scheme sch = scheme_of(s);
+    const orion::frame::BlockPlan plan = orion::frame::block_plan(info_bytes, sch);
+    const orion::frame::ChainOutcome o =
+        orion::frame::decode_chain(llr, n_llr, plan, sch, per_frame_seed, ldpc_rule, ldpc_scale);
+    std::fill(outcome, outcome + 8, 0);
+    outcome[0] = o.error;
+    if (inner_out_len) *inner_out_len = o.inner_out_bits.size();
+    if (o.error) return ORION_OK;
+    if (inner_out_bits) {
+      if (o.inner_out_bits.size() > inner_cap) throw std::invalid_argument("frame decode: inner_out_bits too small");
+      std::copy(o.inner_out_bits.begin(), o.inner_out_bits.end(), inner_out_bits);
+    }
+    std::copy(o.bytes.begin(), o.bytes.end(), bytes);
+    outcome[1] = o.inner_ok;
+    outcome[2] = o.outer_ok;
+    outcome[3] = o.crc_ok;
+    outcome[4] = o.crc_present;
+    outcome[5] = o.outer_present;
+    outcome[6] = static_cast<int32_t>(o.outer_corrected_bytes);
+    outcome[7] = o.is_valid();
+    return ORION_OK;
+  });
+}
+int orion_frame_pack_batch(const orion_frame_scheme* s, const uint8_t* payload, const int64_t* fields,
+                           const int64_t* seeds, size_t nframes, size_t info_len, int out_bytes, uint8_t* out) {
+  if (nframes && ((!payload && !fields && info_len) || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_pack_batch_host(scheme_of(s), payload, ll(fields), ll(seeds), nframes, info_len, out_bytes != 0, out);
+    return ORION_OK;
+  });
+}
+int orion_frame_pack_batch_device(const orion_frame_scheme* s, const uint8_t* payload, const int64_t* fields,
+                                  const int64_t* seeds, size_t nframes, size_t info_len, int out_bytes, uint8_t* out,
+                                  void* stream) {
+  if (nframes && ((!payload && !fields && info_len) || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_pack_batch(scheme_of(s), payload, ll(fields), ll(seeds), nframes, info_len, out_bytes != 0, out,
+                            static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_frame_unpack_batch(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, int in_bytes,
+                             const int64_t* seeds, const int32_t* unsat, size_t n_inner, const int32_t* status,
+                             size_t n_outer, size_t nframes, size_t info_len, uint8_t* payload, uint8_t* flags,
+                             int32_t* corrected, int64_t* fields) {
+  if (nframes && (!in || (!payload && info_len) || !flags || !corrected)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_unpack_batch_host(scheme_of(s), in, in_stride, in_bytes != 0, ll(seeds), unsat, n_inner, status,
+                                   n_outer, nframes, info_len, payload, flags, corrected, ll(fields));
+    return ORION_OK;
+  });
+}
+int orion_frame_unpack_batch_device(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, int in_bytes,
+                                    const int64_t* seeds, const int32_t* unsat, size_t n_inner,
+                                    const int32_t* status, size_t n_outer, size_t nframes, size_t info_len,
+                                    uint8_t* payload, uint8_t* flags, int32_t* corrected, int64_t* fields,
+                                    void* stream) {
+  if (nframes && (!in || (!payload && info_len) || !flags || !corrected)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_unpack_batch(scheme_of(s), in, in_stride, in_bytes != 0, ll(seeds), unsat, n_inner, status, n_outer,
+                              nframes, info_len, payload, flags, corrected, ll(fields),
+                              static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_frame_coded_bits_batch(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride, size_t nbits,
+                                 const int64_t* seeds, size_t nframes, size_t out_len, uint8_t* out) {
+  if (nframes && ((!in && nbits) || (!out && out_len))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_coded_bits_batch_host(scheme_of(s), in, in_stride, nbits, ll(seeds), nframes, out_len, out);
+    return ORION_OK;
+  });
+}
+int orion_frame_coded_bits_batch_device(const orion_frame_scheme* s, const uint8_t* in, size_t in_stride,
+                                        size_t nbits, const int64_t* seeds, size_t nframes, size_t out_len,
+                                        uint8_t* out, void* stream) {
+  if (nframes && ((!in && nbits) || (!out && out_len))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_coded_bits_batch(scheme_of(s), in, in_stride, nbits, ll(seeds), nframes, out_len, out,
+                                  static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_frame_llr_prepare_batch(const orion_frame_scheme* s, const float* in, size_t in_stride, size_t n,
+                                  const int64_t* seeds, size_t nframes, float* out) {
+  if (nframes && n && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_llr_prepare_batch_host(scheme_of(s), in, in_stride, n, ll(seeds), nframes, out);
+    return ORION_OK;
+  });
+}
+int orion_frame_llr_prepare_batch_device(const orion_frame_scheme* s, const float* in, size_t in_stride, size_t n,
+                                         const int64_t* seeds, size_t nframes, float* out, void* stream) {
+  if (nframes && n && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_llr_prepare_batch(scheme_of(s), in, in_stride, n, ll(seeds), nframes, out,
+                                   static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_frame_assemble_batch_device(const void* lead, size_t lead_len, const void* hdr, size_t hdr_len,
+                                      const void* pay, size_t pay_len, size_t nframes, size_t sps, size_t win_start,
+                                      const float* ramp, size_t ramp_len, void* out, void* stream) {
+  if (nframes && ((lead_len && !lead) || (hdr_len && !hdr) || (pay_len && !pay) || !out))
+    return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_assemble_batch(static_cast<const float*>(lead), lead_len, static_cast<const float*>(hdr), hdr_len,
+                                static_cast<const float*>(pay), pay_len, nframes, sps, win_start, ramp, ramp_len,
+                                static_cast<float*>(out), static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_frame_bytes_to_bits_batch(const uint8_t* in, size_t nframes, size_t nbytes, uint8_t* out) {
+  if (nframes && nbytes && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_bytes_to_bits_batch_host(in, nframes, nbytes, out);
+    return ORION_OK;
+  });
+}
+int orion_frame_bytes_to_bits_batch_device(const uint8_t* in, size_t nframes, size_t nbytes, uint8_t* out,
+                                           void* stream) {
+  if (nframes && nbytes && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::frame_bytes_to_bits_batch(in, nframes, nbytes, out, static_cast<hipStream_t>(stream));
     return ORION_OK;
   });
 }

@@ -2594,6 +2594,7 @@ class OfdmConfig:
         self.constellation = constellation
         self.fs, self.rf_hz, self.gain = float(fs), float(rf_hz), float(gain)
         self.rx_window_backoff = 0
+        self._frame = {}
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -2648,6 +2649,87 @@ class OfdmConfig:
         _check(_L.orion_ofdm_config_set_rx_window_backoff(c._h, self.rx_window_backoff))
         c.rx_window_backoff = self.rx_window_backoff
         _check(_L.orion_ofdm_config_set_symbol_window(c._h, self.window_roll_off))
+        c._frame = dict(self.frame_fields)
+        return c
+
+    # ---- the frame-level fields (src/python/ofdm.rs:139-400 over modulate/ofdm.rs:100-340) ----
+    _FRAME_DEFAULTS = {"payload_crc": "crc32", "header_crc": "crc16", "outer_interleaver": None,
+                       "inner_interleaver": None, "scrambler": None, "scrambler_pos": "before_outer",
+                       "header_format": "orion_sdr", "ldpc_decode_rule": "sum_product", "tx_lowpass": None}
+
+    @property
+    def frame_fields(self) -> dict:
+        """The frame layer's settings with the reference's defaults: CRC-32 payload, CRC-16
+        header, the OrionSdr header, no interleavers, no scrambler, sum-product, no TX low-pass."""
+        return {**self._FRAME_DEFAULTS, **getattr(self, "_frame", {})}
+
+    def _with_frame(self, **kw) -> "OfdmConfig":
+        c = self._clone()
+        c._frame.update(kw)
+        c.validate_frame()
+        return c
+
+    def with_interleaver(self, stage, kind, a, b) -> "OfdmConfig":
+        """with_block_interleaver / with_conv_interleaver: stage "inner" or "outer", kind "block"
+        (rows, cols) or "forney" (branches, depth)."""
+        if stage not in ("inner", "outer") or kind not in ("block", "forney"):
+            raise ValueError('interleaver: stage "inner" / "outer", kind "block" / "forney"')
+        return self._with_frame(**{stage + "_interleaver": (kind, int(a), int(b))})
+
+    def with_payload_crc(self, crc) -> "OfdmConfig":
+        return self._with_frame(payload_crc=crc)
+
+    def with_header_crc(self, crc) -> "OfdmConfig":
+        return self._with_frame(header_crc=crc)
+
+    def with_scrambler(self, poly, width, seed=1, per_frame_random=False, position="before_outer") -> "OfdmConfig":
+        return self._with_frame(scrambler=("additive", int(poly), int(width), "per_frame" if per_frame_random else int(seed)),
+                                scrambler_pos=position)
+
+    def with_dvbt_energy_dispersal(self) -> "OfdmConfig":
+        return self._with_frame(scrambler="dvbt", scrambler_pos="before_outer")
+
+    def with_header_format(self, fmt) -> "OfdmConfig":
+        return self._with_frame(header_format=fmt)
+
+    def with_ldpc_decode_rule(self, kind, scale=0.75) -> "OfdmConfig":
+        return self._with_frame(ldpc_decode_rule=("scaled_min_sum", float(scale)) if kind == "scaled_min_sum" else kind)
+
+    def with_tx_lowpass(self, lowpass) -> "OfdmConfig":
+        """A TxLowpass, or None; applied last over the whole frame (host path only)."""
+        if lowpass is not None and not isinstance(lowpass, TxLowpass):
+            raise ValueError("tx_lowpass: a TxLowpass or None")
+        return self._with_frame(tx_lowpass=lowpass)
+
+    def validate_frame(self):
+        """The frame checks of validate (modulate/ofdm.rs:320-340): nonzero interleaver
+        dimensions, known kinds, and a per-frame seed needs a header to travel in. The header
+        formats NoHeader and DvbTps are not built: they raise."""
+        f = self.frame_fields
+        for k in ("payload_crc", "header_crc"):
+            if f[k] not in CRC_KINDS:
+                raise ValueError(f"{k}: one of {sorted(CRC_KINDS)}")
+        for k in ("outer_interleaver", "inner_interleaver"):
+            if f[k] is not None and (f[k][1] <= 0 or f[k][2] <= 0):
+                raise ValueError(f"{k}: dimensions must be nonzero")
+        if f["header_format"] in ("none", "no_header", "dvb_tps", "dvbtps"):
+            raise ValueError("header_format: only 'orion_sdr' is built (NoHeader and DvbTps are not)")
+        if f["header_format"] not in ("orion_sdr", "orionsdr"):
+            raise ValueError("header_format: 'orion_sdr'")
+        if f["scrambler_pos"] not in ("before_outer", "after_inner"):
+            raise ValueError('scrambler position: "before_outer" or "after_inner"')
+        _ldpcf_rule(f["ldpc_decode_rule"])
+        FrameScheme(crc=f["payload_crc"], outer_interleaver=f["outer_interleaver"],
+                    inner_interleaver=f["inner_interleaver"], scrambler=f["scrambler"], scrambler_pos=f["scrambler_pos"])
+
+    def symbol_config(self, constellation) -> "OfdmConfig":
+        """symbol_config (modulate/ofdm_frame.rs:766-779): the bare per-symbol configuration of a
+        constellation over this plan, the RX window back-off kept, no symbol window (the frame
+        modulator tapers in its own post-pass, once)."""
+        n_fft, cp_len, pidx, pval, fs, rf, g, _ = self._args
+        c = OfdmConfig(n_fft, cp_len, self.data_carriers, pidx, pval, fs, rf, g, constellation)
+        _check(_L.orion_ofdm_config_set_rx_window_backoff(c._h, self.rx_window_backoff))
+        c.rx_window_backoff = self.rx_window_backoff
         return c
 
     def with_rx_window_backoff(self, backoff: int) -> "OfdmConfig":
@@ -4121,3 +4203,1107 @@ def bch_decode_batch(bits, t, info_bits=BCH_INFO_BITS, stream=None):
     else:
         _arg_check(_L.orion_bch_decode_batch(*args))
     return msgs, status
+
+
+# ---- the COFDM frame layer's coding chain: CRCs, header fields, scramblers, the block plan,
+# encode_chain / decode_chain and the kernels between the batched codes
+# (src/modulate/ofdm_frame.rs:204-682, src/demodulate/ofdm_frame.rs:351-779, src/codec/crc.rs:89-130,
+# src/fec/frame.rs) ----
+class _FrameSchemeC(C.Structure):
+    _fields_ = [("crc", C.c_int32), ("outer", C.c_int32), ("outer_a", C.c_uint32), ("outer_b", C.c_uint32),
+                ("inner", C.c_int32), ("inner_a", C.c_uint32), ("inner_b", C.c_uint32),
+                ("outer_il", C.c_int32), ("outer_il_a", C.c_uint32), ("outer_il_b", C.c_uint32),
+                ("inner_il", C.c_int32), ("inner_il_a", C.c_uint32), ("inner_il_b", C.c_uint32),
+                ("scrambler", C.c_int32), ("scr_poly", C.c_uint32), ("scr_width", C.c_uint32),
+                ("scr_per_frame", C.c_int32), ("scr_seed", C.c_uint32), ("scrambler_pos", C.c_int32)]
+
+
+def _frame_sigs():
+    vp, sz, i, f, u = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32
+    sp = C.POINTER(_FrameSchemeC)
+    sig = {
+        "orion_frame_crc16": (u, [vp, sz]), "orion_frame_crc32": (u, [vp, sz]),
+        "orion_frame_append_crc": (i, [i, vp, sz, vp]), "orion_frame_check_crc": (i, [i, vp, sz, vp]),
+        "orion_frame_pack_header": (i, [vp, vp]), "orion_frame_unpack_header": (i, [vp, vp]),
+        "orion_frame_reduce_seed": (u, [u, u]),
+        "orion_frame_scramble_bytes": (i, [sp, u, vp, sz]), "orion_frame_scramble_bits": (i, [sp, u, vp, sz]),
+        "orion_frame_apply_pn_to_llrs": (i, [sp, u, vp, sz]), "orion_frame_block_plan": (i, [sp, sz, vp]),
+        "orion_frame_encode_chain": (i, [sp, vp, sz, u, vp, vp]),
+        "orion_frame_decode_chain": (i, [sp, vp, sz, sz, u, i, f, vp, vp, vp, sz, vp]),
+        "orion_frame_pack_batch": (i, [sp, vp, vp, vp, sz, sz, i, vp]),
+        "orion_frame_pack_batch_device": (i, [sp, vp, vp, vp, sz, sz, i, vp, vp]),
+        "orion_frame_unpack_batch": (i, [sp, vp, sz, i, vp, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp]),
+        "orion_frame_unpack_batch_device": (i, [sp, vp, sz, i, vp, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "orion_frame_coded_bits_batch": (i, [sp, vp, sz, sz, vp, sz, sz, vp]),
+        "orion_frame_coded_bits_batch_device": (i, [sp, vp, sz, sz, vp, sz, sz, vp, vp]),
+        "orion_frame_llr_prepare_batch": (i, [sp, vp, sz, sz, vp, sz, vp]),
+        "orion_frame_llr_prepare_batch_device": (i, [sp, vp, sz, sz, vp, sz, vp, vp]),
+        "orion_frame_bytes_to_bits_batch": (i, [vp, sz, sz, vp]),
+        "orion_frame_bytes_to_bits_batch_device": (i, [vp, sz, sz, vp, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_frame_sigs()
+
+CRC_KINDS = {"none": 0, "crc16": 1, "crc32": 2}  # fec/frame.rs:131-151
+HEADER_FIELD_BYTES = 14  # modulate/ofdm_frame.rs:128
+# RxError (fec/frame.rs:59-77) as the codes the frame calls report; 0 is no error
+RX_ERRORS = {"preamble_timeout": 1, "malformed_header": 2, "header_crc_mismatch": 3, "crc_mismatch": 4,
+             "fec_uncorrectable": 5}
+__all__ += ["CRC_KINDS", "HEADER_FIELD_BYTES", "RX_ERRORS", "FrameScheme", "BlockPlan", "ChainOutcome", "crc16",
+            "crc32", "append_crc", "check_and_strip_crc", "bytes_to_bits", "bits_to_bytes", "pack_header_fields",
+            "unpack_header_fields", "scrambler_seed", "scramble_bytes", "scramble_bits", "apply_pn_to_llrs",
+            "block_plan", "symbols_for_coded_bits", "encode_chain", "encode_chain_stages", "decode_chain",
+            "frame_pack_batch", "frame_unpack_batch", "frame_coded_bits_batch", "frame_llr_prepare_batch",
+            "frame_bytes_to_bits_batch", "frame_encode_chain_batch", "frame_decode_chain_batch"]
+
+
+class RxError(Exception):
+    """RxError (fec/frame.rs:59-77): why a received frame could not be delivered. code is the
+    RX_ERRORS value, kind its name."""
+
+    def __init__(self, code):
+        code = RX_ERRORS[code] if isinstance(code, str) else int(code)
+        self.code = code
+        self.kind = {v: k for k, v in RX_ERRORS.items()}.get(code, "unknown")
+        super().__init__(self.kind)
+
+    def __eq__(self, other):
+        return isinstance(other, RxError) and other.code == self.code
+
+    def __hash__(self):
+        return hash(self.code)
+
+
+def _u32(v, what) -> int:
+    v = int(v)
+    if v < 0 or v > 0xFFFFFFFF:
+        raise ValueError(f"{what}: 0 .. 2^32 - 1")
+    return v
+
+
+class FrameScheme:
+    """One logical block's coding chain, encode_chain's arguments after the bytes
+    (modulate/ofdm_frame.rs:621-632):
+
+    crc "none" / "crc16" / "crc32"; outer None, ("bch", t) or ("rs", n, n_parity); inner None,
+    ("ldpc", code) or ("conv", rate[, code]); outer_interleaver / inner_interleaver None, ("block",
+    rows, cols) or ("forney", branches, depth); scrambler None, "dvbt" or ("additive", poly, width,
+    seed) with seed an int (SeedMode::Fixed) or "per_frame" (the seed then comes with each call
+    or frame); scrambler_pos "before_outer" / "after_inner"."""
+
+    def __init__(self, crc="crc32", outer=None, inner=None, outer_interleaver=None, inner_interleaver=None,
+                 scrambler=None, scrambler_pos="before_outer"):
+        c = _FrameSchemeC()
+        if crc not in CRC_KINDS:
+            raise ValueError(f"crc: one of {sorted(CRC_KINDS)}")
+        c.crc = CRC_KINDS[crc]
+        if outer is not None:
+            if outer[0] == "bch" and len(outer) == 2:
+                c.outer, c.outer_a = 1, _u32(outer[1], "t")
+            elif outer[0] in ("rs", "reed_solomon") and len(outer) == 3:
+                c.outer, c.outer_a, c.outer_b = 2, _u32(outer[1], "n"), _u32(outer[2], "n_parity")
+            else:
+                raise ValueError('outer: None, ("bch", t) or ("rs", n, n_parity)')
+        if inner is not None:
+            if inner[0] == "ldpc" and len(inner) == 2:
+                c.inner, c.inner_a = 1, _ldpcf_code(inner[1])
+            elif inner[0] in ("conv", "convolutional") and len(inner) in (2, 3):
+                c.inner, c.inner_b = 2, _fec_rate(inner[1])
+                c.inner_a = _fec_code(inner[2] if len(inner) == 3 else "k5")
+            else:
+                raise ValueError('inner: None, ("ldpc", code) or ("conv", rate[, code])')
+        for name, il in (("outer_il", outer_interleaver), ("inner_il", inner_interleaver)):
+            if il is None:
+                continue
+            if len(il) != 3 or il[0] not in ("block", "forney", "convolutional"):
+                raise ValueError('interleaver: None, ("block", rows, cols) or ("forney", branches, depth)')
+            setattr(c, name, 1 if il[0] == "block" else 2)
+            setattr(c, name + "_a", _u32(il[1], "interleaver"))
+            setattr(c, name + "_b", _u32(il[2], "interleaver"))
+        if scrambler is not None:
+            if scrambler in ("dvbt", "dvb_t"):
+                c.scrambler = 2
+            elif not isinstance(scrambler, str) and len(scrambler) == 4 and scrambler[0] == "additive":
+                c.scrambler, c.scr_poly, c.scr_width = 1, _u32(scrambler[1], "poly"), _u32(scrambler[2], "width")
+                if scrambler[3] == "per_frame":
+                    c.scr_per_frame = 1
+                else:
+                    c.scr_seed = _u32(scrambler[3], "seed")
+            else:
+                raise ValueError('scrambler: None, "dvbt" or ("additive", poly, width, seed | "per_frame")')
+        if scrambler_pos not in ("before_outer", "after_inner"):
+            raise ValueError('scrambler_pos: "before_outer" or "after_inner"')
+        c.scrambler_pos = 0 if scrambler_pos == "before_outer" else 1
+        self._c = c
+        self.crc, self.outer, self.inner = crc, outer, inner
+        self.outer_interleaver, self.inner_interleaver = outer_interleaver, inner_interleaver
+        self.scrambler, self.scrambler_pos = scrambler, scrambler_pos
+        block_plan(0, self)  # the library's check of every parameter
+
+    @property
+    def crc_len(self) -> int:
+        return (0, 2, 4)[self._c.crc]
+
+    @property
+    def per_frame_seed(self) -> bool:
+        return bool(self._c.scr_per_frame)
+
+    def _ptr(self):
+        return C.byref(self._c)
+
+
+def _frame_scheme(scheme) -> FrameScheme:
+    if not isinstance(scheme, FrameScheme):
+        raise ValueError("scheme: a FrameScheme")
+    return scheme
+
+
+def crc16(data) -> int:
+    """CRC-16/CCITT-FALSE (codec/crc.rs:94-108): crc16(b"123456789") == 0x29B1."""
+    b = _bytes_arg(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data)
+    return int(_L.orion_frame_crc16(b.ctypes.data, b.size))
+
+
+def crc32(data) -> int:
+    """CRC-32/ISO-HDLC (codec/crc.rs:116-130): crc32(b"123456789") == 0xCBF43926."""
+    b = _bytes_arg(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data)
+    return int(_L.orion_frame_crc32(b.ctypes.data, b.size))
+
+
+def _crc_kind(crc) -> int:
+    if crc not in CRC_KINDS:
+        raise ValueError(f"crc: one of {sorted(CRC_KINDS)}")
+    return CRC_KINDS[crc]
+
+
+def append_crc(crc, data) -> np.ndarray:
+    """append_crc (modulate/ofdm_frame.rs:237-245): data | its CRC, big-endian."""
+    k, b = _crc_kind(crc), _bytes_arg(data)
+    out = np.zeros(b.size + (0, 2, 4)[k], np.uint8)
+    _arg_check(_L.orion_frame_append_crc(k, b.ctypes.data, b.size, out.ctypes.data))
+    return out
+
+
+def check_and_strip_crc(crc, data):
+    """check_and_strip_crc (modulate/ofdm_frame.rs:249-261): (payload, crc_ok), or None when data
+    is shorter than the CRC field."""
+    k, b = _crc_kind(crc), _bytes_arg(data)
+    clen = (0, 2, 4)[k]
+    if b.size < clen:
+        return None
+    ok = C.c_int32(0)
+    _arg_check(_L.orion_frame_check_crc(k, b.ctypes.data, b.size, C.byref(ok)))
+    return b[:b.size - clen].copy(), bool(ok.value)
+
+
+def bytes_to_bits(data) -> np.ndarray:
+    """bytes_to_bits (modulate/ofdm_frame.rs:207-215): MSB first, one bit per element."""
+    return np.unpackbits(_bytes_arg(data))
+
+
+def bits_to_bytes(bits) -> np.ndarray:
+    """bits_to_bytes (modulate/ofdm_frame.rs:219-234): bit 0 of each element, MSB first; the
+    count must be a whole number of bytes."""
+    b = _bytes_arg(bits, "bits")
+    if b.size % 8:
+        raise ValueError("bit count must be a whole number of bytes")
+    return np.packbits(b & 1)
+
+
+def pack_header_fields(mcs_index, payload_len, sequence_num, flags, scrambler_seed) -> np.ndarray:
+    """pack_header_fields (modulate/ofdm_frame.rs:668-682): the 14 header bytes, big-endian."""
+    if not (0 <= int(mcs_index) <= 255 and 0 <= int(flags) <= 255):
+        raise ValueError("mcs_index and flags are bytes")
+    f = np.array([_u32(mcs_index, "mcs_index"), _u32(payload_len, "payload_len"), _u32(sequence_num, "sequence_num"),
+                  _u32(flags, "flags"), _u32(scrambler_seed, "scrambler_seed")], np.uint32)
+    out = np.zeros(HEADER_FIELD_BYTES, np.uint8)
+    _arg_check(_L.orion_frame_pack_header(f.ctypes.data, out.ctypes.data))
+    return out
+
+
+def unpack_header_fields(data):
+    """The inverse: (mcs_index, payload_len, sequence_num, flags, scrambler_seed)."""
+    b = _bytes_arg(data)
+    if b.size != HEADER_FIELD_BYTES:
+        raise ValueError("a header is 14 field bytes")
+    f = np.zeros(5, np.uint32)
+    _arg_check(_L.orion_frame_unpack_header(b.ctypes.data, f.ctypes.data))
+    return tuple(int(v) for v in f)
+
+
+def scrambler_seed(width, raw) -> int:
+    """build_scrambler's seed (modulate/ofdm_frame.rs:277-289): raw reduced to width bits (all 32
+    when width >= 32), a zero mapped to 1."""
+    return int(_L.orion_frame_reduce_seed(_u32(width, "width"), _u32(raw, "raw")))
+
+
+def scramble_bytes(scheme, data, per_frame_seed=0) -> np.ndarray:
+    """scramble_bytes (modulate/ofdm_frame.rs:300-312) of the scheme's scrambler: self-inverse."""
+    s, b = _frame_scheme(scheme), _bytes_arg(data).copy()
+    _arg_check(_L.orion_frame_scramble_bytes(s._ptr(), _u32(per_frame_seed, "per_frame_seed"), b.ctypes.data, b.size))
+    return b
+
+
+def scramble_bits(scheme, bits, per_frame_seed=0) -> np.ndarray:
+    """scramble_bits (modulate/ofdm_frame.rs:650-655): an Additive scrambler over bits packed MSB
+    first, so bit i meets PN step 8 (i // 8) + 7 - i % 8; other kinds leave the bits alone."""
+    s, b = _frame_scheme(scheme), _bytes_arg(bits, "bits").copy()
+    _arg_check(_L.orion_frame_scramble_bits(s._ptr(), _u32(per_frame_seed, "per_frame_seed"), b.ctypes.data, b.size))
+    return b
+
+
+def apply_pn_to_llrs(scheme, llr, per_frame_seed=0) -> np.ndarray:
+    """apply_pn_to_llrs (demodulate/ofdm_frame.rs:767-779): the sign of llr[i] flipped where
+    scramble_bits flips bit i."""
+    s = _frame_scheme(scheme)
+    l = np.ascontiguousarray(llr, np.float32).copy()
+    if l.ndim != 1:
+        raise ValueError("llr: expected a 1-D float32 array")
+    _arg_check(_L.orion_frame_apply_pn_to_llrs(s._ptr(), _u32(per_frame_seed, "per_frame_seed"), l.ctypes.data, l.size))
+    return l
+
+
+class BlockPlan:
+    """BlockPlan (modulate/ofdm_frame.rs:320-334): every intermediate length of one block."""
+    __slots__ = ("info_bytes", "framed_bytes", "outer_coded_bits", "outer_il_bits", "inner_coded_bits", "coded_bits")
+
+    def __init__(self, *v):
+        for name, x in zip(self.__slots__, v):
+            setattr(self, name, int(x))
+
+    def astuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, BlockPlan) and self.astuple() == other.astuple()
+
+    def __repr__(self):
+        return "BlockPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
+
+
+def block_plan(info_bytes, scheme) -> BlockPlan:
+    """block_plan (modulate/ofdm_frame.rs:362-427)."""
+    info_bytes = int(info_bytes)
+    if info_bytes < 0:
+        raise ValueError("info_bytes: not negative")
+    c = scheme._c if isinstance(scheme, FrameScheme) else None
+    if c is None:
+        raise ValueError("scheme: a FrameScheme")
+    v = (C.c_size_t * 6)()
+    _arg_check(_L.orion_frame_block_plan(C.byref(c), info_bytes, v))
+    return BlockPlan(*v)
+
+
+def symbols_for_coded_bits(n_data_carriers, bits_per_carrier, bits) -> int:
+    """symbols_for_coded_bits (modulate/ofdm_frame.rs:431-438)."""
+    bps = int(n_data_carriers) * int(bits_per_carrier)
+    return -(-int(bits) // bps)
+
+
+def encode_chain_stages(data, scheme, per_frame_seed=0):
+    """encode_chain_stages (modulate/ofdm_frame.rs:572-615) on the host: (outer_il_bits, coded)."""
+    s, b = _frame_scheme(scheme), _bytes_arg(data)
+    p = block_plan(b.size, s)
+    coded, oil = np.zeros(p.coded_bits, np.uint8), np.zeros(p.outer_il_bits, np.uint8)
+    _arg_check(_L.orion_frame_encode_chain(s._ptr(), b.ctypes.data, b.size, _u32(per_frame_seed, "per_frame_seed"),
+                                           coded.ctypes.data, oil.ctypes.data))
+    return oil, coded
+
+
+def encode_chain(data, scheme, per_frame_seed=0) -> np.ndarray:
+    """encode_chain (modulate/ofdm_frame.rs:621-646) on the host: the coded bits of one block."""
+    return encode_chain_stages(data, scheme, per_frame_seed)[1]
+
+
+class ChainOutcome:
+    """ChainOutcome (demodulate/ofdm_frame.rs:559-644)."""
+
+    def __init__(self, data, inner_ok, outer_ok, crc_ok, crc_present, outer_present, outer_corrected_bytes,
+                 inner_out_bits):
+        self.bytes, self.inner_ok, self.outer_ok, self.crc_ok = data, bool(inner_ok), bool(outer_ok), bool(crc_ok)
+        self.crc_present, self.outer_present = bool(crc_present), bool(outer_present)
+        self.outer_corrected_bytes, self.inner_out_bits = outer_corrected_bytes, inner_out_bits
+
+    def is_valid(self) -> bool:
+        return self.crc_ok if self.crc_present else self.outer_ok if self.outer_present else self.inner_ok
+
+
+def decode_chain(llr, info_bytes, scheme, per_frame_seed=0, ldpc_rule="sum_product"):
+    """decode_chain (demodulate/ofdm_frame.rs:651-725) on the host under block_plan(info_bytes,
+    scheme): float32 LLRs, positive meaning bit 0 -> a ChainOutcome; raises
+    RxError("malformed_header") when too few bits come out of the decoders."""
+    s = _frame_scheme(scheme)
+    r, scale = _ldpcf_rule(ldpc_rule)
+    l = np.ascontiguousarray(llr, np.float32)
+    if l.ndim != 1:
+        raise ValueError("llr: expected a 1-D float32 array")
+    p = block_plan(info_bytes, s)
+    cap = max(p.coded_bits, p.outer_il_bits, l.size) + 1024
+    data, inner = np.zeros(p.info_bytes, np.uint8), np.zeros(cap, np.uint8)
+    out, n_inner = np.zeros(8, np.int32), C.c_size_t(0)
+    _arg_check(_L.orion_frame_decode_chain(s._ptr(), l.ctypes.data, l.size, p.info_bytes,
+                                           _u32(per_frame_seed, "per_frame_seed"), r, scale, data.ctypes.data,
+                                           out.ctypes.data, inner.ctypes.data, cap, C.byref(n_inner)))
+    if out[0]:
+        raise RxError(int(out[0]))
+    return ChainOutcome(data, out[1], out[2], out[3], out[4], out[5], None if out[6] < 0 else int(out[6]),
+                        inner[:n_inner.value].copy())
+
+
+def _frame_i64(x, what, ns, cols, like, dev):
+    """x as int64 (ns,) / (ns, cols) where like lives (None stays None)."""
+    if x is None:
+        return None
+    shape = (ns,) if cols is None else (ns, cols)
+    if dev:
+        import torch
+
+        t = x if _is_torch(x) else torch.as_tensor(np.ascontiguousarray(x, np.int64))
+        t = t.to(device=like.device, dtype=torch.int64).contiguous()
+    else:
+        t = np.ascontiguousarray(x, np.int64)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what}: expected shape {shape}")
+    return t
+
+
+def _frame_ptr(a, dev):
+    return None if a is None else _rs_ptr(a, dev)
+
+
+def _contig(a, dev):
+    return a.contiguous() if dev else np.ascontiguousarray(a)
+
+
+def frame_pack_batch(payloads, scheme, fields=None, seeds=None, out_bytes=False, stream=None):
+    """The head of the encode chain for a batch on the GPU in one launch, one wave per frame:
+    uint8 (nframes, info_len) -> uint8 (nframes, framed * 8) bits, MSB first, or with out_bytes
+    (nframes, framed) bytes: append_crc, then scramble_bytes when the scheme's scrambler sits
+    before the outer code. fields (payloads None): int64 (nframes, 5) mcs_index, payload_len,
+    sequence_num, flags, scrambler_seed, packed as pack_header_fields (a host array is range
+    checked as there; of a device tensor the kernel takes the low 8 / 32 bits). seeds: int64 (nframes,)
+    per-frame seeds (required by a "per_frame" scrambler). A numpy array (-> numpy) or a
+    contiguous torch CUDA tensor (-> a torch tensor on its device, queued on torch's current
+    stream or on stream)."""
+    s = _frame_scheme(scheme)
+    if (payloads is None) == (fields is None):
+        raise ValueError("frame_pack_batch: payloads or fields")
+    if fields is not None:
+        dev = _is_torch(fields)
+        ns, info_len = int(fields.shape[0]), HEADER_FIELD_BYTES
+        if not dev:  # as pack_header_fields refuses them; a device tensor is not read back: the
+            # kernel takes the low 8 bits of mcs_index and flags, the low 32 of the others
+            fa = np.asarray(fields)
+            if fa.ndim != 2 or fa.shape[1] != 5 or (fa < 0).any() or (fa[:, [0, 3]] > 255).any() or (fa > 0xFFFFFFFF).any():
+                raise ValueError("fields: (nframes, 5), mcs_index and flags bytes, the others 0 .. 2^32 - 1")
+        f = _frame_i64(fields, "fields", ns, 5, fields, dev)
+        p, like = None, f
+    else:
+        p, dev = _fec2_arg(payloads, "payloads", "uint8", (2,))
+        ns, info_len = int(p.shape[0]), int(p.shape[1])
+        f, like = None, p
+    sd = _frame_seeds(s, seeds, ns, like, dev, s._c.scrambler_pos == 0)
+    framed = info_len + s.crc_len
+    out = _rs_out(like, dev, (ns, framed if out_bytes else framed * 8), "uint8")
+    args = (s._ptr(), _frame_ptr(p, dev), _frame_ptr(f, dev), _frame_ptr(sd, dev), ns, info_len, int(bool(out_bytes)),
+            _rs_ptr(out, dev))
+    if dev:
+        _arg_check(_L.orion_frame_pack_batch_device(*args, SyncEngine._stream(like, stream)))
+    else:
+        _arg_check(_L.orion_frame_pack_batch(*args))
+    return out
+
+
+def _frame_seeds(s, seeds, ns, like, dev, here):
+    """The per-frame seeds a call passes down: required where a "per_frame" scrambler acts."""
+    if s.per_frame_seed and here and seeds is None:
+        raise ValueError("seeds: the scheme's scrambler takes a seed per frame")
+    return _frame_i64(seeds, "seeds", ns, None, like, dev) if s.per_frame_seed and here else None
+
+
+def frame_unpack_batch(x, info_len, scheme, seeds=None, in_bytes=False, unsat=None, status=None, header=False,
+                       stream=None):
+    """The tail of the decode chain for a batch on the GPU in one launch, one wave per frame: the
+    first framed * 8 elements of each row of x, uint8 (nframes, >= framed * 8), are the framed
+    bits (in_bytes: the first framed elements its bytes), as the outer decoders write them.
+    They are packed, descrambled (a scrambler before the outer code) and their CRC is checked.
+    unsat int32 (nframes, n_inner) and status int32 (nframes, n_outer) are the decoders' per-word
+    outputs. Returns a dict: payload uint8 (nframes, info_len), inner_ok (all unsat == 0),
+    outer_ok (all status >= 0), crc_ok, valid (ChainOutcome.is_valid) as bool (nframes,),
+    corrected int32 (nframes,) the sum of the non-negative status entries, and with header
+    (info_len 14) fields int64 (nframes, 5). A numpy array (-> numpy) or a contiguous torch CUDA
+    tensor (-> torch tensors on its device, queued on torch's current stream or on stream)."""
+    s = _frame_scheme(scheme)
+    a, dev = _fec2_arg(x, "x", "uint8", (2,))
+    ns, stride, info_len = int(a.shape[0]), int(a.shape[1]), int(info_len)
+    if info_len < 0 or stride < (info_len + s.crc_len) * (1 if in_bytes else 8):
+        raise ValueError("x: a row holds at least the framed block")
+    if header and info_len != HEADER_FIELD_BYTES:
+        raise ValueError("a header is 14 field bytes")
+    n_in = n_out = 0
+    if unsat is not None:
+        unsat, d2 = _fec2_arg(unsat, "unsat", "int32", (2,))
+        n_in = int(unsat.shape[1])
+        if d2 != dev or int(unsat.shape[0]) != ns:
+            raise ValueError("unsat: (nframes, n_inner) where x lives")
+    if status is not None:
+        status, d2 = _fec2_arg(status, "status", "int32", (2,))
+        n_out = int(status.shape[1])
+        if d2 != dev or int(status.shape[0]) != ns:
+            raise ValueError("status: (nframes, n_outer) where x lives")
+    sd = _frame_seeds(s, seeds, ns, a, dev, s._c.scrambler_pos == 0)
+    payload, flags = _rs_out(a, dev, (ns, info_len), "uint8"), _rs_out(a, dev, (ns, 4), "uint8")
+    corrected = _rs_out(a, dev, (ns,), "int32")
+    fields = _rs_out(a, dev, (ns, 5), "int64") if header else None
+    args = (s._ptr(), _rs_ptr(a, dev), stride, int(bool(in_bytes)), _frame_ptr(sd, dev), _frame_ptr(unsat, dev), n_in,
+            _frame_ptr(status, dev), n_out, ns, info_len, _rs_ptr(payload, dev), _rs_ptr(flags, dev),
+            _rs_ptr(corrected, dev), _frame_ptr(fields, dev))
+    if dev:
+        _arg_check(_L.orion_frame_unpack_batch_device(*args, SyncEngine._stream(a, stream)))
+    else:
+        _arg_check(_L.orion_frame_unpack_batch(*args))
+    out = {"payload": payload, "inner_ok": flags[:, 0] != 0, "outer_ok": flags[:, 1] != 0, "crc_ok": flags[:, 2] != 0,
+           "valid": flags[:, 3] != 0, "corrected": corrected}
+    if header:
+        out["fields"] = fields
+    return out
+
+
+def frame_coded_bits_batch(bits, scheme, nbits=None, out_len=None, seeds=None, stream=None):
+    """The rows ofdm_modulate_batch takes, for a batch on the GPU in one launch: uint8 (nframes,
+    >= nbits) -> uint8 (nframes, out_len): the first nbits elements of each row (default: all),
+    scramble_bits applied when the scheme's Additive scrambler sits after the inner code, then
+    zeros up to out_len (default nbits). A numpy array (-> numpy) or a contiguous torch CUDA
+    tensor (-> a torch tensor on its device, queued on torch's current stream or on stream)."""
+    s = _frame_scheme(scheme)
+    b, dev = _fec2_arg(bits, "bits", "uint8", (2,))
+    ns, stride = int(b.shape[0]), int(b.shape[1])
+    nbits = stride if nbits is None else int(nbits)
+    out_len = nbits if out_len is None else int(out_len)
+    if not 0 <= nbits <= min(stride, out_len):
+        raise ValueError("nbits: within a row of bits and within out_len")
+    sd = _frame_seeds(s, seeds, ns, b, dev, s._c.scrambler_pos == 1)
+    out = _rs_out(b, dev, (ns, out_len), "uint8")
+    args = (s._ptr(), _rs_ptr(b, dev), stride, nbits, _frame_ptr(sd, dev), ns, out_len, _rs_ptr(out, dev))
+    if dev:
+        _arg_check(_L.orion_frame_coded_bits_batch_device(*args, SyncEngine._stream(b, stream)))
+    else:
+        _arg_check(_L.orion_frame_coded_bits_batch(*args))
+    return out
+
+
+def frame_llr_prepare_batch(llr, n, scheme, seeds=None, stream=None):
+    """The mirror of frame_coded_bits_batch: float32 (nframes, >= n), as ofdm_demodulate_batch(...,
+    llr=True) gives them -> float32 (nframes, n): the first n LLRs of each row, apply_pn_to_llrs
+    applied when the scheme's Additive scrambler sits after the inner code (the sign bit alone
+    changes: NaN, zeros and infinities keep every other bit). A numpy array (-> numpy) or a
+    contiguous torch CUDA tensor (-> a torch tensor on its device, queued on torch's current
+    stream or on stream)."""
+    s = _frame_scheme(scheme)
+    l, dev = _fec2_arg(llr, "llr", "float32", (2,))
+    ns, stride, n = int(l.shape[0]), int(l.shape[1]), int(n)
+    if not 0 <= n <= stride:
+        raise ValueError("n: within a row of llr")
+    sd = _frame_seeds(s, seeds, ns, l, dev, s._c.scrambler_pos == 1)
+    out = _rs_out(l, dev, (ns, n), "float32")
+    args = (s._ptr(), _rs_ptr(l, dev), stride, n, _frame_ptr(sd, dev), ns, _rs_ptr(out, dev))
+    if dev:
+        _arg_check(_L.orion_frame_llr_prepare_batch_device(*args, SyncEngine._stream(l, stream)))
+    else:
+        _arg_check(_L.orion_frame_llr_prepare_batch(*args))
+    return out
+
+
+def frame_bytes_to_bits_batch(x, stream=None):
+    """uint8 (nframes, nbytes) -> (nframes, nbytes * 8), MSB first, on the GPU in one launch:
+    what joins the byte-domain Reed-Solomon encoder to the bit-domain inner encoders. A numpy
+    array (-> numpy) or a contiguous torch CUDA tensor (-> torch, on torch's current stream or
+    on stream)."""
+    a, dev = _fec2_arg(x, "x", "uint8", (2,))
+    ns, nb = int(a.shape[0]), int(a.shape[1])
+    out = _rs_out(a, dev, (ns, nb * 8), "uint8")
+    if dev:
+        _arg_check(_L.orion_frame_bytes_to_bits_batch_device(a.data_ptr(), ns, nb, out.data_ptr(),
+                                                             SyncEngine._stream(a, stream)))
+    else:
+        _arg_check(_L.orion_frame_bytes_to_bits_batch(a.ctypes.data, ns, nb, out.ctypes.data))
+    return out
+
+
+def _frame_device_scheme(s):
+    """What the batched chain takes of a scheme; the rest runs on the host path (encode_chain /
+    decode_chain) alone."""
+    c = s._c
+    if c.outer_il == 1:
+        raise ValueError("the batched chain takes no outer Block interleaver (the host chain does)")
+    if c.outer_il == 2 and c.outer != 2:
+        raise ValueError("the batched chain takes the Forney outer interleaver over Reed-Solomon words only")
+    if c.inner_il == 2 or (c.inner_il == 1 and c.inner == 0):
+        raise ValueError("the batched chain takes a Block inner interleaver fused into an inner code, nothing else")
+    inner_il = (int(c.inner_il_a), int(c.inner_il_b)) if c.inner_il == 1 else None
+    rate = {v: k for k, v in FEC_RATES.items()}.get(int(c.inner_b))
+    code = {v: k for k, v in FEC_CODES.items()}.get(int(c.inner_a))
+    return c, inner_il, rate, code
+
+
+def _pad_cols(a, width, dev):
+    if int(a.shape[1]) == width:
+        return a
+    if dev:
+        import torch
+
+        return torch.nn.functional.pad(a, (0, width - int(a.shape[1])))
+    return np.pad(a, ((0, 0), (0, width - a.shape[1])))
+
+
+class _TorchOn:
+    """torch's own work (pads, slices, allocations) inside a chain call goes where the launches
+    go: with a raw stream handle, torch's current stream is that stream for the call."""
+
+    def __init__(self, like, stream):
+        self._ctx = None
+        if stream is not None and _is_torch(like):
+            import torch
+
+            self._ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=like.device))
+
+    def __enter__(self):
+        if self._ctx is not None:
+            self._ctx.__enter__()
+
+    def __exit__(self, *exc):
+        if self._ctx is not None:
+            self._ctx.__exit__(*exc)
+
+
+def frame_encode_chain_batch(payloads, scheme, fields=None, seeds=None, out_len=None, stream=None):
+    """encode_chain for a batch of equal-length blocks on the GPU: uint8 (nframes, info_len) (or
+    header fields, see frame_pack_batch) -> uint8 (nframes, out_len) coded bits, zero-padded
+    from plan.coded_bits to out_len (default: no padding), row k equal to encode_chain of block k
+    under seeds[k]. The launches: frame_pack_batch -> bch_encode_batch / rs_encode_batch ->
+    forney_interleave_batch -> ldpc_family_encode_batch / conv_encode_batch (a Block inner
+    interleaver fused) -> frame_coded_bits_batch. Not taken (ValueError; the host chain takes
+    them): an outer Block interleaver, the Forney interleaver without Reed-Solomon, an inner
+    interleaver without an inner code."""
+    with _TorchOn(payloads if payloads is not None else fields, stream):
+        return _frame_encode_chain(payloads, _frame_scheme(scheme), fields, seeds, out_len, stream)
+
+
+def _frame_encode_chain(payloads, s, fields, seeds, out_len, stream):
+    c, inner_il, rate, code = _frame_device_scheme(s)
+    dev = _is_torch(payloads if payloads is not None else fields)
+    info_len = HEADER_FIELD_BYTES if payloads is None else int(payloads.shape[1])
+    plan = block_plan(info_len, s)
+    x = frame_pack_batch(payloads, s, fields=fields, seeds=seeds, out_bytes=c.outer == 2 or c.outer_il == 2,
+                         stream=stream)
+    ns = int(x.shape[0])
+    if c.outer == 1:
+        x = bch_encode_batch(x, int(c.outer_a), stream=stream)
+    elif c.outer == 2:
+        n, k = int(c.outer_a), int(c.outer_a) - int(c.outer_b)
+        ncw = -(-plan.framed_bytes // k)
+        x = rs_encode_batch(_contig(_pad_cols(x, ncw * k, dev).reshape(ns, ncw, k), dev), n, int(c.outer_b),
+                            stream=stream)
+        if c.outer_il != 2:
+            x = frame_bytes_to_bits_batch(x.reshape(ns, ncw * n), stream=stream)
+    if c.outer_il == 2:
+        x = forney_interleave_batch(x, int(c.outer_il_a), int(c.outer_il_b), bits=True, stream=stream)
+    if c.inner == 1:
+        x = ldpc_family_encode_batch(x, {v: k for k, v in LDPC_CODES.items()}[int(c.inner_a)], interleaver=inner_il,
+                                     stream=stream)
+    elif c.inner == 2:
+        x = conv_encode_batch(x, rate, code, interleaver=inner_il, stream=stream)
+    if int(x.shape[1]) != plan.coded_bits:
+        raise OrionError(f"frame chain: {int(x.shape[1])} coded bits where the plan has {plan.coded_bits}")
+    return frame_coded_bits_batch(x, s, out_len=plan.coded_bits if out_len is None else out_len, seeds=seeds,
+                                  stream=stream)
+
+
+def frame_decode_chain_batch(llr, info_len, scheme, seeds=None, ldpc_rule="sum_product", header=False, stream=None):
+    """decode_chain for a batch of equal-length blocks on the GPU: float32 (nframes, >=
+    plan.coded_bits) LLRs, as ofdm_demodulate_batch(..., llr=True) gives them -> the dict of
+    frame_unpack_batch plus inner_out_bits uint8 (nframes, ...), the inner decoder's untrimmed
+    output; entry k equals decode_chain of row k under seeds[k] in every field. The launches:
+    frame_llr_prepare_batch -> ldpc_family_decode_batch (50 iterations) / conv_viterbi_batch ->
+    bch_decode_batch / rs_decode_batch (the Forney deinterleaver fused), over
+    plan.outer_coded_bits alone -> frame_unpack_batch. The same schemes as
+    frame_encode_chain_batch."""
+    with _TorchOn(llr, stream):
+        return _frame_decode_chain(llr, info_len, _frame_scheme(scheme), seeds, ldpc_rule, header, stream)
+
+
+def _frame_decode_chain(llr, info_len, s, seeds, ldpc_rule, header, stream):
+    c, inner_il, rate, code = _frame_device_scheme(s)
+    plan = block_plan(info_len, s)
+    l, dev = _fec2_arg(llr, "llr", "float32", (2,))
+    if int(l.shape[1]) < plan.coded_bits:
+        raise ValueError(f"llr: a row holds at least the plan's {plan.coded_bits} coded bits")
+    if int(l.shape[1]) != plan.coded_bits or (c.scrambler == 1 and c.scrambler_pos == 1):
+        l = frame_llr_prepare_batch(l, plan.coded_bits, s, seeds=seeds, stream=stream)
+    unsat = None
+    if c.inner == 1:
+        name = {v: k for k, v in LDPC_CODES.items()}[int(c.inner_a)]
+        bits, unsat, _ = ldpc_family_decode_batch(l, name, max_iter=50, rule=ldpc_rule, interleaver=inner_il,
+                                                  stream=stream)
+        nblk, kk = plan.inner_coded_bits // Ldpc(name).n, Ldpc(name).k
+        if int(unsat.shape[1]) != nblk:  # interleaver padding of a block or more is not the code's
+            bits, unsat = _contig(bits[:, :nblk * kk], dev), _contig(unsat[:, :nblk], dev)
+    elif c.inner == 2:
+        bits = conv_viterbi_batch(l, plan.outer_il_bits, rate, code, interleaver=inner_il, stream=stream)
+    elif dev:
+        import torch
+
+        bits = (l <= 0).to(torch.uint8)
+    else:
+        bits = (l <= 0).astype(np.uint8)
+    inner_out = bits
+    x, status, in_bytes = bits, None, False
+    if c.outer == 2:
+        n = int(c.outer_a)
+        de = (int(c.outer_il_a), int(c.outer_il_b)) if c.outer_il == 2 else None
+        x = _contig(bits[:, :plan.outer_il_bits if de else plan.outer_coded_bits], dev)
+        msgs, status = rs_decode_batch(x, n, int(c.outer_b), bits=True, deinterleave=de, stream=stream)
+        x, in_bytes = msgs.reshape(int(msgs.shape[0]), -1), True
+    elif c.outer == 1:
+        x, status = bch_decode_batch(_contig(bits[:, :plan.outer_coded_bits], dev), int(c.outer_a), stream=stream)
+    out = frame_unpack_batch(x, info_len, s, seeds=seeds, in_bytes=in_bytes, unsat=unsat, status=status,
+                             header=header, stream=stream)
+    out["inner_out_bits"] = inner_out
+    return out
+
+
+# ---- the COFDM frame layer at a known start: OfdmFrameMod / OfdmFrameDemod
+# (src/modulate/ofdm_frame.rs:125-202, 781-987, src/demodulate/ofdm_frame.rs:862-1255,
+# src/sync/ofdm_sync.rs:142-352, src/fec/frame.rs) ----
+_L.orion_frame_assemble_batch_device.restype = C.c_int
+_L.orion_frame_assemble_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                 C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p]
+HEADER_CONSTELLATION, HEADER_LDPC = "bpsk", "n512r12"  # modulate/ofdm_frame.rs:131-135
+__all__ += ["RxError", "FrameMetadata", "FramePacket", "Mcs", "McsTable", "OfdmPreamble", "generate_ofdm_preamble",
+            "OfdmFrameMod", "OfdmFrameDemod", "frame_assemble_batch", "HEADER_CONSTELLATION", "HEADER_LDPC"]
+
+
+class FrameMetadata:
+    """FrameMetadata (fec/frame.rs:41-56)."""
+
+    def __init__(self, sequence_num=0, mcs_index=0, flags=0):
+        self.sequence_num, self.mcs_index, self.flags = _u32(sequence_num, "sequence_num"), int(mcs_index), int(flags)
+        if not (0 <= self.mcs_index <= 255 and 0 <= self.flags <= 255):
+            raise ValueError("mcs_index and flags are bytes")
+
+    def __eq__(self, o):
+        return isinstance(o, FrameMetadata) and (self.sequence_num, self.mcs_index, self.flags) == \
+            (o.sequence_num, o.mcs_index, o.flags)
+
+    def __repr__(self):
+        return f"FrameMetadata(sequence_num={self.sequence_num}, mcs_index={self.mcs_index}, flags={self.flags})"
+
+
+class FramePacket:
+    """FramePacket (fec/frame.rs:24-34): metadata plus the payload bytes."""
+
+    def __init__(self, metadata, payload):
+        self.metadata = metadata
+        self.payload = _bytes_arg(np.frombuffer(bytes(payload), np.uint8) if isinstance(payload, (bytes, bytearray))
+                                  else payload, "payload").copy()
+
+    def __eq__(self, o):
+        return isinstance(o, FramePacket) and self.metadata == o.metadata and np.array_equal(self.payload, o.payload)
+
+
+class Mcs:
+    """Mcs (modulate/ofdm_frame.rs:140-159): the payload's constellation, inner and outer FEC,
+    the codes in FrameScheme's vocabulary."""
+
+    def __init__(self, constellation, inner=None, outer=None):
+        _ofdm_order(constellation)
+        FrameScheme(inner=inner, outer=outer)
+        self.constellation, self.inner, self.outer = constellation, inner, outer
+
+
+class McsTable:
+    """McsTable (modulate/ofdm_frame.rs:163-202): mcs_index -> Mcs; both ends share it."""
+
+    def __init__(self, entries=()):
+        self.entries = list(entries)
+
+    @classmethod
+    def default_ladder(cls) -> "McsTable":
+        return cls([Mcs(c, ("ldpc", "n512r12"), ("bch", 8)) for c in ("bpsk", "qpsk", "qam16", "qam64")])
+
+    def add(self, constellation, inner=None, outer=None) -> int:
+        if len(self.entries) >= 256:
+            raise ValueError("an MCS table holds at most 256 entries")
+        self.entries.append(Mcs(constellation, inner, outer))
+        return len(self.entries) - 1
+
+    def get(self, mcs_index):
+        return self.entries[mcs_index] if 0 <= mcs_index < len(self.entries) else None
+
+    def __len__(self):
+        return len(self.entries)
+
+
+class OfdmPreamble:
+    """OfdmPreamble (sync/ofdm_sync.rs): num_repeats raw repeats of repeat_len samples, then an
+    optional training symbol of training_n_fft + training_cp_len samples."""
+
+    def __init__(self, num_repeats, repeat_len):
+        self.num_repeats, self.repeat_len, self.training = int(num_repeats), int(repeat_len), None
+        if self.num_repeats < 0 or self.repeat_len < 0:
+            raise ValueError("OfdmPreamble: counts are not negative")
+
+    def with_training_symbol(self, n_fft, cp_len) -> "OfdmPreamble":
+        p = OfdmPreamble(self.num_repeats, self.repeat_len)
+        p.training = (int(n_fft), int(cp_len))
+        return p
+
+    @property
+    def total_len(self) -> int:
+        return self.num_repeats * self.repeat_len + (sum(self.training) if self.training else 0)
+
+
+def _unit_sequence(n, seed):
+    """pseudo_random_unit_sequence (ofdm_sync.rs:335-352): xorshift64, each part +-1/sqrt(2) by the
+    sign of (state as f32) / 2^64 - 0.5."""
+    state, mask, out = seed, (1 << 64) - 1, np.zeros(n, np.complex64)
+    h = np.float32(0.70710678118654752440)  # FRAC_1_SQRT_2
+
+    def nxt():
+        nonlocal state
+        state ^= (state << 13) & mask
+        state ^= state >> 7
+        state ^= (state << 17) & mask
+        return np.float32(np.float32(np.uint64(state)) / np.float32(2.0 ** 64)) - np.float32(0.5)
+
+    for i in range(n):
+        re = h if nxt() >= 0 else -h
+        im = h if nxt() >= 0 else -h
+        out[i] = complex(re, im)
+    return out
+
+
+def _cf32_scale(x, g):
+    g = np.float32(g)
+    out = np.empty(x.shape, np.complex64)
+    out.real, out.imag = x.real * g, x.imag * g
+    return out
+
+
+def generate_ofdm_preamble(cfg, num_repeats, repeat_len, training_n_fft=None, training_cp_len=None) -> np.ndarray:
+    """generate_ofdm_preamble (sync/ofdm_sync.rs:142-332) on the host: the band-limited repeat base
+    (bins that are multiples of n_fft / repeat_len inside the occupied span, DC skipped, scaled
+    to twice a data symbol's RMS), or the wideband sequence when the geometry admits none;
+    then the training symbol loaded on the plan's occupied bins alone; cfg.gain applied."""
+    n_fft, half, n_data = cfg.n_fft, cfg.occupied_half_carriers, cfg.num_data_carriers
+    repeat_len, num_repeats = int(repeat_len), int(num_repeats)
+    base = None
+    if repeat_len > 0 and n_fft % repeat_len == 0 and half > 0:
+        k = n_fft // repeat_len
+        loaded = [b for i in range(1, half + 1) for b in (i, n_fft - i) if i % k == 0]
+        if loaded:
+            freq = np.zeros(n_fft, np.complex64)
+            freq[loaded] = _unit_sequence(len(loaded), 0x4F46444D50524531)
+            t = fft_host(freq, n_fft, inverse=True)[:repeat_len]
+            acc = np.float32(0.0)
+            for c in t:
+                acc = np.float32(acc + np.float32(np.float32(c.real * c.real) + np.float32(c.imag * c.imag)))
+            rms = np.sqrt(np.float32(acc / np.float32(repeat_len)))
+            if rms > 0:
+                target = np.float32(np.float32(np.float32(2.0) * np.sqrt(np.float32(n_data))) / np.float32(n_fft))
+                t = _cf32_scale(t, np.float32(target / rms))
+            base = t
+    if base is None:
+        base = _unit_sequence(repeat_len, 0x4F46444D50524531)
+    parts = [base] * num_repeats
+    if training_n_fft is not None:
+        tn, tcp = int(training_n_fft), int(training_cp_len or 0)
+        freq = ofdm_tables(n_fft=tn)[2]
+        occ = cfg.occupied_bins()
+        if occ.size:
+            load = np.zeros(tn, bool)
+            load[occ[occ < tn]] = True
+            freq = np.where(load, freq, np.complex64(0)).astype(np.complex64)
+        t = fft_host(np.ascontiguousarray(freq), tn, inverse=True)
+        parts.append(np.concatenate([t[tn - tcp:], t]) if tcp else t)
+    out = np.concatenate(parts).astype(np.complex64) if parts else np.zeros(0, np.complex64)
+    return _cf32_scale(out, cfg.gain) if np.float32(cfg.gain) != np.float32(1.0) else out
+
+
+def frame_assemble_batch(lead, header_iq, payload_iq, sps, win_start, ramp=None, stream=None):
+    """The frames' IQ on the GPU in one launch: complex64 lead (lead_len,) shared by all frames,
+    header_iq (nframes, hdr_len), payload_iq (nframes, pay_len) -> (nframes, frame_len). With
+    ramp (SymbolWindow's, float32) every whole symbol of sps samples from win_start on is
+    tapered on its first and last len(ramp) samples, the frame modulator's window post-pass.
+    Contiguous torch CUDA tensors, queued on torch's current stream or on stream."""
+    import torch
+
+    for t, nd, dt in ((lead, 1, torch.complex64), (header_iq, 2, torch.complex64), (payload_iq, 2, torch.complex64)):
+        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous() or t.dim() != nd or t.dtype != dt:
+            raise ValueError("frame_assemble_batch: contiguous complex64 CUDA tensors, lead 1-D, the others 2-D")
+    ns = int(header_iq.shape[0])
+    if int(payload_iq.shape[0]) != ns:
+        raise ValueError("frame_assemble_batch: one header and one payload row per frame")
+    nr = 0 if ramp is None else int(ramp.numel())
+    if nr and (not ramp.is_cuda or not ramp.is_contiguous() or ramp.dtype != torch.float32):
+        raise ValueError("ramp: a contiguous float32 CUDA tensor")
+    ll, hl, pl = int(lead.numel()), int(header_iq.shape[1]), int(payload_iq.shape[1])
+    out = torch.empty((ns, ll + hl + pl), dtype=torch.complex64, device=header_iq.device)
+    _arg_check(_L.orion_frame_assemble_batch_device(lead.data_ptr(), ll, header_iq.data_ptr(), hl, payload_iq.data_ptr(),
+                                                    pl, ns, int(sps), int(win_start), ramp.data_ptr() if nr else None,
+                                                    nr, out.data_ptr(), SyncEngine._stream(header_iq, stream)))
+    return out
+
+
+class _FrameLayer:
+    """What the frame modulator and demodulator share: the schemes, plans and symbol-layer
+    handles of a configuration and an MCS table."""
+
+    def __init__(self, cfg, mcs_table):
+        if not isinstance(cfg, OfdmConfig) or not isinstance(mcs_table, McsTable) or len(mcs_table) < 1:
+            raise ValueError("an OfdmConfig and an McsTable of at least one entry")
+        if cfg.rf_hz != 0.0:  # assert_baseband, modulate/ofdm_frame.rs:815-822
+            raise ValueError(f"OFDM frame assembly is baseband-only: got rf_hz = {cfg.rf_hz} Hz. Modulate at rf_hz = 0.0 "
+                             "and upconvert the whole burst with one continuous Rotator.")
+        cfg.validate_frame()
+        self.cfg, self.mcs_table, self.f = cfg, mcs_table, cfg.frame_fields
+        self.sps, self.n_data = cfg.samples_per_ofdm_symbol, cfg.num_data_carriers
+        self.header_scheme = FrameScheme(crc=self.f["header_crc"], inner=("ldpc", HEADER_LDPC))
+        self.header_plan = block_plan(HEADER_FIELD_BYTES, self.header_scheme)
+        self.header_symbols = symbols_for_coded_bits(self.n_data, 1, self.header_plan.coded_bits)
+        self._sym, self._mods, self._demods = {}, {}, {}
+
+    def scheme(self, mcs) -> FrameScheme:
+        f = self.f
+        return FrameScheme(crc=f["payload_crc"], outer=mcs.outer, inner=mcs.inner, outer_interleaver=f["outer_interleaver"],
+                           inner_interleaver=f["inner_interleaver"], scrambler=f["scrambler"],
+                           scrambler_pos=f["scrambler_pos"])
+
+    def payload_symbols(self, mcs, plan) -> int:
+        return symbols_for_coded_bits(self.n_data, (1, 2, 4, 6, 8)[_ofdm_order(mcs.constellation)], plan.coded_bits)
+
+    def symcfg(self, constellation):
+        if constellation not in self._sym:
+            self._sym[constellation] = self.cfg.symbol_config(constellation)
+        return self._sym[constellation]
+
+    def mod(self, constellation):
+        if constellation not in self._mods:
+            self._mods[constellation] = OfdmMod(self.symcfg(constellation))
+        return self._mods[constellation]
+
+    def demod(self, constellation):
+        if constellation not in self._demods:
+            self._demods[constellation] = OfdmDemod(self.symcfg(constellation), equalizer=None)
+        return self._demods[constellation]
+
+    def _device_ok(self):
+        if self.f["tx_lowpass"] is not None:
+            raise ValueError("the batched path takes no TX low-pass (the host path does)")
+
+
+class OfdmFrameMod(_FrameLayer):
+    """OfdmFrameMod (modulate/ofdm_frame.rs:781-987): FramePacket -> IQ,
+    [S&C repeats + training symbol][header: BPSK, n512r12, header_crc][payload per its MCS],
+    every CP-bearing symbol from the training symbol on tapered once when the plan has a window
+    roll-off, then the TX low-pass when one is set. modulate_frame is the library's host code;
+    modulate_frames the same frames batched on the GPU."""
+
+    def __init__(self, cfg, mcs_table, preamble):
+        super().__init__(cfg, mcs_table)
+        if not isinstance(preamble, OfdmPreamble):
+            raise ValueError("preamble: an OfdmPreamble")
+        self.preamble = preamble
+        tr = preamble.training or (None, None)
+        self._lead = generate_ofdm_preamble(cfg, preamble.num_repeats, preamble.repeat_len, tr[0], tr[1])
+        self._win_start = preamble.num_repeats * preamble.repeat_len
+        self._roll = cfg.window_roll_off
+        self._dev = {}
+
+    def frame_len(self, mcs_index, payload_len) -> int:
+        mcs = self.mcs_table.get(mcs_index)
+        if mcs is None:
+            raise ValueError("mcs_index must be in the MCS table")
+        return self._lead.size + (self.header_symbols + self.payload_symbols(mcs, block_plan(payload_len, self.scheme(mcs)))) * self.sps
+
+    def _window(self, out):
+        if self._roll == 0 or out.size <= self._win_start:
+            return out
+        k = (out.size - self._win_start) // self.sps
+        end = self._win_start + k * self.sps
+        out[self._win_start:end] = ofdm_window(np.ascontiguousarray(out[self._win_start:end]), self.sps, self._roll)
+        return out
+
+    def modulate_frame(self, frame, per_frame_seed=0) -> np.ndarray:
+        """modulate_frame (modulate/ofdm_frame.rs:867-958) on the host."""
+        md = frame.metadata
+        mcs = self.mcs_table.get(md.mcs_index)
+        if mcs is None:
+            raise ValueError("mcs_index must be in the MCS table")
+        seed = _u32(per_frame_seed, "per_frame_seed")
+        fields = pack_header_fields(md.mcs_index, frame.payload.size, md.sequence_num, md.flags, seed)
+        hdr = self.mod(HEADER_CONSTELLATION).modulate_host(encode_chain(fields, self.header_scheme, 0))
+        pay = self.mod(mcs.constellation).modulate_host(encode_chain(frame.payload, self.scheme(mcs), seed))
+        out = self._window(np.concatenate([self._lead, hdr, pay]).astype(np.complex64))
+        lp = self.f["tx_lowpass"]
+        return lp.apply(out) if lp is not None else out
+
+    def modulate_frames(self, payloads, mcs_index, sequence_nums=None, flags=None, seeds=None, stream=None):
+        """A batch sharing one MCS and one payload length on the GPU: uint8 (nframes,
+        payload_len) -> complex64 (nframes, frame_len), row k equal to modulate_frame of frame k
+        (sequence_nums[k], flags[k], seeds[k]; default 0). The launches: the header and payload
+        chains (frame_encode_chain_batch), ofdm_modulate_batch for each, frame_assemble_batch.
+        numpy in -> numpy out; a contiguous torch CUDA tensor stays resident, queued on torch's
+        current stream or on stream."""
+        import torch
+
+        self._device_ok()
+        mcs = self.mcs_table.get(int(mcs_index))
+        if mcs is None:
+            raise ValueError("mcs_index must be in the MCS table")
+        if not _is_torch(payloads):
+            p, _ = _fec2_arg(payloads, "payloads", "uint8", (2,))
+            return self.modulate_frames(torch.from_numpy(p).cuda(), mcs_index, sequence_nums, flags, seeds, stream).cpu().numpy()
+        p, _ = _fec2_arg(payloads, "payloads", "uint8", (2,))
+        with _TorchOn(p, stream):
+            ns, n = int(p.shape[0]), int(p.shape[1])
+            sch = self.scheme(mcs)
+            plan = block_plan(n, sch)
+
+            def col(x, what):
+                if x is None:
+                    return torch.zeros(ns, dtype=torch.int64, device=p.device)
+                return _frame_i64(x, what, ns, None, p, True)
+
+            sd = col(seeds, "seeds")
+            fields = torch.stack([torch.full((ns,), int(mcs_index), dtype=torch.int64, device=p.device),
+                                  torch.full((ns,), n, dtype=torch.int64, device=p.device),
+                                  col(sequence_nums, "sequence_nums"), col(flags, "flags"), sd], dim=1).contiguous()
+            hmod, pmod = self.mod(HEADER_CONSTELLATION), self.mod(mcs.constellation)
+            hbits = frame_encode_chain_batch(None, self.header_scheme, fields=fields,
+                                             out_len=self.header_symbols * hmod.bits_per_ofdm_symbol, stream=stream)
+            pbits = frame_encode_chain_batch(p, sch, seeds=sd if sch.per_frame_seed else None,
+                                             out_len=self.payload_symbols(mcs, plan) * pmod.bits_per_ofdm_symbol,
+                                             stream=stream)
+            hiq = ofdm_modulate_batch(hmod, hbits, stream=stream)
+            piq = ofdm_modulate_batch(pmod, pbits, stream=stream)
+            key = str(p.device)
+            if key not in self._dev:  # the shared lead and the ramp, uploaded once per modulator
+                ramp = ofdm_tables(symbol_len=self.sps, roll_off=self._roll)[4]
+                self._dev[key] = (torch.from_numpy(self._lead).to(p.device), torch.from_numpy(ramp).to(p.device))
+            lead, ramp = self._dev[key]
+            return frame_assemble_batch(lead, hiq, piq, self.sps, self._win_start, ramp if ramp.numel() else None,
+                                        stream=stream)
+
+
+class OfdmFrameDemod(_FrameLayer):
+    """OfdmFrameDemod at a known start (demodulate/ofdm_frame.rs:862-1255 with no channel
+    estimate): IQ from the first sample after the preamble and training symbol -> FramePacket.
+    decode is the library's host code and raises RxError; decode_frames decodes a batch on the
+    GPU and reports the same outcome per frame."""
+
+    def _llrs_host(self, constellation, iq, n_sym):
+        soft = self.demod(constellation).process_host(np.ascontiguousarray(iq[:n_sym * self.sps]))
+        return ofdm_llr(constellation, soft)
+
+    def decode(self, iq) -> FramePacket:
+        """decode (demodulate/ofdm_frame.rs:1231-1254): truncated input -> malformed_header, an
+        invalid header -> header_crc_mismatch, an MCS index outside the table ->
+        malformed_header, an invalid payload -> crc_mismatch; the payload is trimmed to the
+        declared length. The header is decoded under sum-product whatever the payload's rule."""
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        nh = self.header_symbols
+        if iq.size < nh * self.sps:
+            raise RxError("malformed_header")
+        header = decode_chain(self._llrs_host(HEADER_CONSTELLATION, iq, nh), HEADER_FIELD_BYTES, self.header_scheme, 0,
+                              "sum_product")
+        if not header.is_valid():
+            raise RxError("header_crc_mismatch")
+        mcs_index, payload_len, seq, flags, seed = unpack_header_fields(header.bytes)
+        mcs = self.mcs_table.get(mcs_index)
+        if mcs is None:
+            raise RxError("malformed_header")
+        sch = self.scheme(mcs)
+        try:
+            plan = block_plan(payload_len, sch)
+        except ValueError:
+            raise RxError("malformed_header") from None
+        n_sym = self.payload_symbols(mcs, plan)
+        body = iq[nh * self.sps:]
+        if body.size < n_sym * self.sps:
+            raise RxError("malformed_header")
+        out = decode_chain(self._llrs_host(mcs.constellation, body, n_sym), payload_len, sch, seed,
+                           self.f["ldpc_decode_rule"])
+        if not out.is_valid():
+            raise RxError("crc_mismatch")
+        return FramePacket(FrameMetadata(seq, mcs_index, flags), out.bytes[:payload_len])
+
+    def decode_frames(self, iq, stream=None) -> dict:
+        """A batch on the GPU: complex64 (nframes, n), each row from the first sample after the
+        preamble and training symbol. Every header is decoded on the device; the parsed fields
+        and their validity come to the host in one small copy (the one synchronisation: the
+        payload geometry is data); frames are grouped by (mcs_index, payload_len) and each
+        group's payload chain is launched. Returns numpy arrays per frame: error (0 or the
+        RX_ERRORS code decode raises), mcs_index, sequence_num, flags, payload_len, inner_ok,
+        outer_ok, crc_ok, and payloads, a list of uint8 arrays (empty where error != 0). numpy
+        or a contiguous torch CUDA tensor, queued on torch's current stream or on stream."""
+        import torch
+
+        if not _is_torch(iq):
+            if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != 2:
+                raise ValueError("iq: expected a 2-D complex64 array")
+            return self.decode_frames(torch.from_numpy(np.ascontiguousarray(iq)).cuda(), stream)
+        if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+            raise ValueError("iq: expected a contiguous 2-D complex64 CUDA tensor")
+        ns, n = int(iq.shape[0]), int(iq.shape[1])
+        res = {k: np.zeros(ns, np.int64) for k in ("error", "mcs_index", "sequence_num", "flags", "payload_len")}
+        res.update({k: np.zeros(ns, bool) for k in ("inner_ok", "outer_ok", "crc_ok")})
+        res["payloads"] = [np.zeros(0, np.uint8) for _ in range(ns)]
+        hl = self.header_symbols * self.sps
+        if n < hl or ns == 0:
+            res["error"][:] = RX_ERRORS["malformed_header"]
+            return res
+        with _TorchOn(iq, stream):
+            hllr = ofdm_demodulate_batch(self.demod(HEADER_CONSTELLATION), iq[:, :hl].contiguous(), bits=False, llr=True,
+                                         stream=stream)[2]
+            h = frame_decode_chain_batch(hllr, HEADER_FIELD_BYTES, self.header_scheme, ldpc_rule="sum_product",
+                                         header=True, stream=stream)
+            if stream is not None:
+                torch.cuda.current_stream(iq.device).synchronize()
+            head = torch.cat([h["fields"], h["valid"].to(torch.int64)[:, None]], dim=1).cpu().numpy()  # the one copy
+            E = RX_ERRORS
+            valid = head[:, 5] != 0
+            res["error"][~valid] = E["header_crc_mismatch"]
+            for col, key in ((0, "mcs_index"), (1, "payload_len"), (2, "sequence_num"), (3, "flags")):
+                res[key][valid] = head[valid, col]
+            known = valid & (head[:, 0] < len(self.mcs_table)) & (head[:, 1] <= (1 << 16))  # the device chain's block limit
+            res["error"][valid & ~known] = E["malformed_header"]
+            key = head[:, 0] * (1 << 33) + head[:, 1]
+            groups = {(int(v) >> 33, int(v) & ((1 << 33) - 1)): np.flatnonzero(known & (key == v)) for v in np.unique(key[known])}
+            for (mcs_index, plen), rows in groups.items():
+                mcs = self.mcs_table.get(mcs_index)
+                sch = self.scheme(mcs)
+                plen_sym = self.payload_symbols(mcs, block_plan(plen, sch)) * self.sps
+                if n - hl < plen_sym:
+                    res["error"][rows] = RX_ERRORS["malformed_header"]
+                    continue
+                idx = torch.from_numpy(rows).to(iq.device)
+                body = iq.index_select(0, idx)[:, hl:hl + plen_sym].contiguous()
+                llr = ofdm_demodulate_batch(self.demod(mcs.constellation), body, bits=False, llr=True, stream=stream)[2]
+                seeds = h["fields"].index_select(0, idx)[:, 4].contiguous() if sch.per_frame_seed else None
+                out = frame_decode_chain_batch(llr, plen, sch, seeds=seeds, ldpc_rule=self.f["ldpc_decode_rule"], stream=stream)
+                if stream is not None:
+                    torch.cuda.current_stream(iq.device).synchronize()
+                pay = out["payload"].cpu().numpy()
+                flg = torch.stack([out["inner_ok"], out["outer_ok"], out["crc_ok"], out["valid"]], dim=1).cpu().numpy()
+                res["inner_ok"][rows], res["outer_ok"][rows], res["crc_ok"][rows] = flg[:, 0], flg[:, 1], flg[:, 2]
+                res["error"][rows[~flg[:, 3]]] = E["crc_mismatch"]
+                for j in np.flatnonzero(flg[:, 3]):
+                    res["payloads"][rows[j]] = pay[j]
+        return res
