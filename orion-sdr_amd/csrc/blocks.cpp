@@ -40,6 +40,13 @@ void DevBuf::upload(const void* h, size_t bytes, hipStream_t s) {
   ORION_HIP(hipStreamSynchronize(s));
 }
 
+StagedIn::StagedIn(const void* src, size_t bytes, size_t slack) : buf_(bytes + slack), given_(src != nullptr) {
+  if (src && bytes) ORION_HIP(hipMemcpy(buf_.as<void>(), src, bytes, hipMemcpyHostToDevice));
+}
+void stage_out(void* dst, const DevBuf& src, size_t bytes) {
+  if (dst && bytes) ORION_HIP(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost));
+}
+
 // ------------------------------------------------------------------- Block --
 hipStream_t Block::host_stream() {
   if (!hs_) ORION_HIP(hipStreamCreateWithFlags(&hs_, hipStreamNonBlocking));

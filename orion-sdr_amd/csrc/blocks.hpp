@@ -48,6 +48,24 @@ class DevBuf {
   size_t n_ = 0;
 };
 
+// The staging of a host-memory entry point: its inputs copied to the device (StagedIn), the
+// device entry on the null stream, its outputs copied back (stage_out), hipDeviceSynchronize.
+// A staged input is a device buffer of bytes + slack with the caller's bytes in it; nothing is
+// copied when the caller passed no pointer or no bytes.
+class StagedIn {
+ public:
+  StagedIn(const void* src, size_t bytes, size_t slack = 16);
+  template <class T> T* as() const { return buf_.as<T>(); }
+  // null when the caller passed no pointer: an optional argument of the device entry
+  template <class T> T* opt() const { return given_ ? buf_.as<T>() : nullptr; }
+
+ private:
+  DevBuf buf_;
+  bool given_;
+};
+// Copies the first bytes of src to the caller's dst; a null or empty destination is skipped.
+void stage_out(void* dst, const DevBuf& src, size_t bytes);
+
 class Block {
  public:
   virtual ~Block();

@@ -40,6 +40,13 @@ __device__ __forceinline__ void lds_barrier() {
 // in order); also a compiler fence. For hand-offs inside one wave: no barrier.
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// The XOR of v over the 64 lanes of the wave, the same in every lane.
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v ^= __shfl_xor(v, off, 64);
+  return v;
+}
+
 // A read-only table the host wrote before the launch, read at wave-uniform indices: in
 // the constant address space the compiler reads it with scalar loads (one s_load per
 // 4-16 dwords for the wave) instead of a vector load per use whose 64 lanes each

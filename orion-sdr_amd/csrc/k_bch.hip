@@ -3,8 +3,8 @@
 // (bch.rs:105-125), for the code of any t <= 31 shortened to any n.
 //
 // The decode. One wave64 per word, kBchWaves words per workgroup; the GF(2^8) exp/log tables
-// (rs.hpp make_gf_tables) sit in LDS, as do the word, its syndromes and the locator of each
-// wave. Lane l holds elements l, l + 64, l + 128, l + 192 of the word; an element is set when
+// and the wave algebra on them are gf256_wave.hpp's; the tables sit in LDS, as do the word, its
+// syndromes and the locator of each wave. Lane l holds elements l, l + 64, l + 128, l + 192 of the word; an element is set when
 // it is nonzero. Position p has code degree 254 - p whatever n is, so syndrome j of a set
 // element is exp[j (254 - p) mod 255]: the lane steps that exponent by 254 - p per syndrome
 // and never multiplies; four syndromes are packed in a word and XOR-reduced across the wave.
@@ -24,14 +24,12 @@
 #include <algorithm>
 
 #include "bch_blocks.hpp"
-#include "hip_common.hpp"
+#include "gf256_wave.hpp"
 
 namespace orion {
 
 namespace {
 constexpr int kBchWaves = 4;  // words per workgroup
-
-__constant__ __attribute__((aligned(16))) rs::GfTables d_bch_gf = rs::make_gf_tables();
 
 // what a launch's words share; every field is wave-uniform
 struct BchGeom {
@@ -39,55 +37,23 @@ struct BchGeom {
   uint64_t stream_len;  // elements of one input stream
 };
 
-__device__ __forceinline__ uint32_t bch_wave_xor(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v ^= __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t bch_gf_mul(const uint8_t* ex, const uint8_t* lg, uint32_t a, uint32_t b) {
-  const uint32_t v = ex[lg[a] + lg[b]];
-  return a != 0 && b != 0 ? v : 0u;
-}
-
 // The 2 t syndromes of the word whose elements lane, lane + 64, .. this lane holds in r, four
-// to a word of sw (S_j in byte (j - 1) % 4 of sw[(j - 1) / 4]), the same in every lane.
-// Returns how many are nonzero.
+// to a word of sw (S_j in byte (j - 1) % 4 of sw[(j - 1) / 4]), the same in every lane: S_1
+// comes first, so a set element starts at its degree. Returns how many are nonzero.
 __device__ __forceinline__ uint32_t bch_syndromes(const uint8_t* ex, const uint32_t r[4], uint32_t lane,
-                                                  const BchGeom& g, uint32_t sw[16]) {
-  uint32_t e[4], d[4];
+                                                  const BchGeom& g, uint32_t (&sw)[16]) {
+  uint32_t start[4];
   bool nz[4];
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    const uint32_t p = lane + 64u * a;
-    nz[a] = p < g.n && r[a] != 0;
-    d[a] = p < 255u ? 254u - p : 0u;
-    e[a] = d[a];
+    nz[a] = lane + 64u * a < g.n && r[a] != 0;
+    start[a] = gf256::degree(lane + 64u * a);
   }
   uint32_t count = 0;
+  gf256::syndromes(ex, lane, start, nz, 2u * g.t, sw, [&](uint32_t word) {
 #pragma unroll
-  for (int w = 0; w < 16; ++w) {
-    uint32_t word = 0;
-    if (4u * w < 2u * g.t) {  // uniform
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        if (4u * w + jj < 2u * g.t) {
-          uint32_t byte = 0;
-#pragma unroll
-          for (int a = 0; a < 4; ++a) {
-            if (nz[a]) byte ^= ex[e[a]];
-            e[a] += d[a];
-            if (e[a] >= 255u) e[a] -= 255u;
-          }
-          word |= byte << (8 * jj);
-        }
-      }
-      word = bch_wave_xor(word);
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) count += (word >> (8 * jj)) & 255u ? 1u : 0u;
-    }
-    sw[w] = word;
-  }
+    for (int jj = 0; jj < 4; ++jj) count += (word >> (8 * jj)) & 255u ? 1u : 0u;
+  });
   return count;
 }
 }  // namespace
@@ -95,12 +61,12 @@ __device__ __forceinline__ uint32_t bch_syndromes(const uint8_t* ex, const uint3
 __global__ __launch_bounds__(64 * kBchWaves) void k_bch_decode(const uint8_t* __restrict__ in, long long total_cw,
                                                               BchGeom g, uint8_t* __restrict__ msgs,
                                                               int32_t* __restrict__ status) {
-  __shared__ uint32_t s_tab[192];  // exp[512] | log[256]
+  __shared__ uint32_t s_tab[gf256::kTableWords];  // exp[512] | log[256]
   __shared__ uint8_t s_word[kBchWaves][256];
   __shared__ uint32_t s_syn[kBchWaves][16];
   __shared__ uint8_t s_sig[kBchWaves][64];
   const uint32_t tid = threadIdx.x;
-  if (tid < 192) s_tab[tid] = reinterpret_cast<const uint32_t*>(&d_bch_gf)[tid];
+  gf256::load_tables(s_tab, tid);
   __syncthreads();  // the only workgroup barrier: a wave without a word leaves after it
   const uint8_t* ex = reinterpret_cast<const uint8_t*>(s_tab);
   const uint8_t* lg = ex + 512;
@@ -132,46 +98,15 @@ __global__ __launch_bounds__(64 * kBchWaves) void k_bch_decode(const uint8_t* __
     }
     wave_lds_fence();
 
-    // Berlekamp-Massey, bch.rs:318-356; sigma_i and b_i in lane i
-    uint32_t sigma = lane == 0 ? 1u : 0u, bpoly = sigma;
-    uint32_t L = 0, m = 1;
-    for (uint32_t it = 0; it < 2u * g.t; ++it) {  // step n = it + 1
-      uint32_t term = 0;
-      if (lane >= 1 && lane <= L) term = bch_gf_mul(ex, lg, sigma, syn[it - lane]);  // L <= it
-      const uint32_t delta = bch_wave_xor(term) ^ syn[it];
-      if (delta == 0) {
-        ++m;
-      } else {
-        uint32_t sh = __shfl_up(bpoly, m, 64);
-        if (lane < m) sh = 0;
-        const uint32_t next = sigma ^ bch_gf_mul(ex, lg, delta, sh);
-        if (2u * L <= it) {
-          L = it + 1u - L;
-          bpoly = bch_gf_mul(ex, lg, sigma, ex[255u - lg[delta]]);
-          m = 1;
-        } else {
-          ++m;
-        }
-        sigma = next;
-      }
-    }
-    sig[lane] = static_cast<uint8_t>(sigma);
+    sig[lane] = static_cast<uint8_t>(gf256::berlekamp_massey(ex, lg, syn, lane, 2u * g.t));  // sigma_i in lane i
     wave_lds_fence();
 
-    // Chien, bch.rs:171-195: sigma(2^-d) = sum sigma_i exp[(log sigma_i + i (255 - d)) mod 255]
+    // Chien, bch.rs:171-195: a transmitted root flips its element and is counted
     uint32_t n_found = 0;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const uint32_t d = lane + 64u * a;
-      const uint32_t step = (255u - d % 255u) % 255u;
-      uint32_t e = 0, val = 0;
-      for (uint32_t i = 0; i <= 2u * g.t; ++i) {
-        const uint32_t c = sig[i];
-        if (c != 0) val ^= ex[lg[c] + e];
-        e += step;
-        if (e >= 255u) e -= 255u;
-      }
-      const bool applied = d < 255u && val == 0 && d >= 255u - g.n;
+      const bool applied = d < 255u && gf256::chien(ex, lg, sig, d, 2u * g.t) == 0 && d >= 255u - g.n;
       if (applied) word[254u - d] ^= 1u;
       n_found += static_cast<uint32_t>(__popcll(__ballot(applied)));
     }
@@ -290,12 +225,12 @@ void bch_decode_batch_host(size_t t, size_t info_bits, const uint8_t* in, size_t
   bch_counts(nstreams, ncw);
   if (nstreams == 0) return;
   const size_t ib = nstreams * nb, mb = nstreams * ncw * code.k(), sb = nstreams * ncw * sizeof(int32_t);
-  DevBuf d_in(ib + 16), d_msgs(mb + 16), d_status(sb);
-  ORION_HIP(hipMemcpy(d_in.as<void>(), in, ib, hipMemcpyHostToDevice));
+  StagedIn d_in(in, ib);
+  DevBuf d_msgs(mb + 16), d_status(sb);
   bch_decode_batch(t, info_bits, d_in.as<uint8_t>(), nstreams, nb, d_msgs.as<uint8_t>(), d_status.as<int32_t>(),
                    nullptr);
-  ORION_HIP(hipMemcpy(msgs, d_msgs.as<void>(), mb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(status, d_status.as<void>(), sb, hipMemcpyDeviceToHost));
+  stage_out(msgs, d_msgs, mb);
+  stage_out(status, d_status, sb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -327,10 +262,10 @@ void bch_encode_batch_host(size_t t, size_t info_bits, const uint8_t* bits, size
   bch_counts(nstreams, ncw);
   if (nstreams == 0) return;
   const size_t ib = nstreams * nbits, ob = nstreams * ncw * code.n();
-  DevBuf d_in(ib + 16), d_out(ob + 16);
-  ORION_HIP(hipMemcpy(d_in.as<void>(), bits, ib, hipMemcpyHostToDevice));
+  StagedIn d_in(bits, ib);
+  DevBuf d_out(ob + 16);
   bch_encode_batch(t, info_bits, d_in.as<uint8_t>(), nstreams, nbits, d_out.as<uint8_t>(), nullptr);
-  ORION_HIP(hipMemcpy(coded, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(coded, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 

@@ -32,8 +32,8 @@
 // bits too). Every loop is bounded by n_steps.
 #include <algorithm>
 
+#include "code_dev.hpp"
 #include "fec_blocks.hpp"
-#include "hip_common.hpp"
 
 namespace orion {
 
@@ -63,10 +63,7 @@ __device__ __forceinline__ float fec_fetch(const float* __restrict__ L, const Fe
   uint32_t src = p;
   if (g.block) {  // uniform
     const uint32_t b0 = p / g.block * g.block;
-    if (b0 + g.block <= g.n_llr) {  // a full block: out[r cols + c] = in[c rows + r]
-      const uint32_t q = p - b0, r = q / g.cols, c = q - r * g.cols;
-      src = b0 + c * g.rows + r;
-    }
+    if (b0 + g.block <= g.n_llr) src = b0 + block_il_offset(p - b0, g.rows, g.cols);  // a full block
   }
   return L[src];
 }
@@ -207,8 +204,8 @@ __global__ __launch_bounds__(256) void k_conv_encode(const uint8_t* __restrict__
   const uint32_t o = static_cast<uint32_t>(idx - stream * g.lim);
   uint32_t p = o;
   if (g.block) {
-    const uint32_t b0 = o / g.block * g.block, q = o - b0, c = q / g.rows, r = q - c * g.rows;
-    p = b0 + r * g.cols + c;
+    const uint32_t b0 = o / g.block * g.block;
+    p = b0 + block_il_offset(o - b0, g.cols, g.rows);  // the inverse map
   }
   uint8_t v = 0;
   if (p < g.coded_len) {
@@ -281,11 +278,11 @@ void fec_viterbi_host(int code, int rate, const float* llr, size_t nstreams, siz
   if (nstreams == 0) return;
   const size_t lb = nstreams * n_llr * sizeof(float), bb = nstreams * info_bits;
   const size_t wb = fec::viterbi_work_bytes(fec::code_spec(code).reg_bits, nstreams, info_bits);
-  DevBuf d_llr(lb + 16), d_bits(bb + 16), d_work(wb);
-  if (lb) ORION_HIP(hipMemcpy(d_llr.as<void>(), llr, lb, hipMemcpyHostToDevice));
+  StagedIn d_llr(llr, lb);
+  DevBuf d_bits(bb + 16), d_work(wb);
   fec_viterbi(code, rate, d_llr.as<float>(), nstreams, n_llr, info_bits, rows, cols, d_bits.as<uint8_t>(),
               d_work.as<void>(), wb, nullptr);
-  ORION_HIP(hipMemcpy(bits, d_bits.as<void>(), bb, hipMemcpyDeviceToHost));
+  stage_out(bits, d_bits, bb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -317,10 +314,10 @@ void fec_encode_batch_host(int code, int rate, const uint8_t* info, size_t nstre
   if (nstreams > fec::kMaxStreams) throw std::invalid_argument("fec: nstreams above 2^24");
   if (nstreams == 0) return;
   const size_t ib = nstreams * info_bits, ob = nstreams * out_len;
-  DevBuf d_info(ib + 16), d_out(ob + 16);
-  ORION_HIP(hipMemcpy(d_info.as<void>(), info, ib, hipMemcpyHostToDevice));
+  StagedIn d_info(info, ib);
+  DevBuf d_out(ob + 16);
   fec_encode_batch(code, rate, d_info.as<uint8_t>(), nstreams, info_bits, rows, cols, d_out.as<uint8_t>(), nullptr);
-  ORION_HIP(hipMemcpy(coded, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(coded, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 

@@ -67,12 +67,6 @@ __device__ __forceinline__ uint32_t gf2_apply(const uint32_t (&col)[32], uint32_
   return r;
 }
 
-__device__ __forceinline__ uint32_t frame_wave_xor(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v ^= __shfl_xor(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ uint32_t pn_seed(const PnGeom& p, const long long* seeds, long long f) {
   if (p.kind == frame::kScrDvbT) return rs::kDvbTPrbsInit;
   const uint32_t raw = seeds ? static_cast<uint32_t>(seeds[f]) : p.fixed_seed;
@@ -140,7 +134,7 @@ __device__ __forceinline__ uint32_t crc_combine(const FrameGeom& g, uint32_t lan
     const uint32_t t = gf2_apply(g.crc_adv[s], crc);
     crc = (e >> s) & 1u ? t : crc;
   }
-  crc = frame_wave_xor(lane < g.nact ? crc : 0u);
+  crc = wave_xor(lane < g.nact ? crc : 0u);
   return g.crc == frame::kCrc32 ? ~crc : crc;
 }
 
@@ -559,30 +553,17 @@ void frame_assemble_batch(const float* lead, size_t lead_len, const float* hdr, 
 }
 
 // ---- host-memory variants: copy in, one launch, copy out --------------------------------------
-namespace {
-struct Up {
-  DevBuf buf;
-  Up(const void* src, size_t bytes) : buf(bytes + 16) {
-    if (src && bytes) ORION_HIP(hipMemcpy(buf.as<void>(), src, bytes, hipMemcpyHostToDevice));
-  }
-};
-void down(void* dst, DevBuf& src, size_t bytes) {
-  if (dst && bytes) ORION_HIP(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost));
-}
-}  // namespace
-
 void frame_pack_batch_host(const frame::Scheme& sch, const uint8_t* payload, const long long* fields,
                            const long long* seeds, size_t nframes, size_t info_len, bool out_bytes, uint8_t* out) {
   frame_counts(nframes, info_len, fields != nullptr);
   const size_t framed = info_len + frame::crc_len(sch.crc), ob = nframes * framed * (out_bytes ? 1 : 8);
   if (nframes == 0) return;
-  Up d_pay(fields ? nullptr : payload, fields ? 0 : nframes * info_len), d_f(fields, fields ? nframes * 40 : 0),
+  StagedIn d_pay(fields ? nullptr : payload, fields ? 0 : nframes * info_len), d_f(fields, fields ? nframes * 40 : 0),
       d_s(seeds, seeds ? nframes * 8 : 0);
   DevBuf d_out(ob + 16);
-  frame_pack_batch(sch, d_pay.buf.as<uint8_t>(), fields ? d_f.buf.as<long long>() : nullptr,
-                   seeds ? d_s.buf.as<long long>() : nullptr, nframes, info_len, out_bytes, d_out.as<uint8_t>(),
-                   nullptr);
-  down(out, d_out, ob);
+  frame_pack_batch(sch, d_pay.as<uint8_t>(), d_f.opt<long long>(), d_s.opt<long long>(), nframes, info_len, out_bytes,
+                   d_out.as<uint8_t>(), nullptr);
+  stage_out(out, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -596,17 +577,16 @@ void frame_unpack_batch_host(const frame::Scheme& sch, const uint8_t* in, size_t
       n_outer > kFrameMaxRow)
     throw std::invalid_argument("frame unpack: a row holds the framed block and at most 2^27 elements, at most 2^24 words per frame");
   if (nframes == 0) return;
-  Up d_in(in, nframes * in_stride), d_s(seeds, seeds ? nframes * 8 : 0), d_u(unsat, unsat ? nframes * n_inner * 4 : 0),
-      d_st(status, status ? nframes * n_outer * 4 : 0);
+  StagedIn d_in(in, nframes * in_stride), d_s(seeds, seeds ? nframes * 8 : 0),
+      d_u(unsat, unsat ? nframes * n_inner * 4 : 0), d_st(status, status ? nframes * n_outer * 4 : 0);
   DevBuf d_pay(nframes * info_len + 16), d_fl(nframes * 4 + 16), d_c(nframes * 4 + 16), d_f(nframes * 40 + 16);
-  frame_unpack_batch(sch, d_in.buf.as<uint8_t>(), in_stride, in_bytes, seeds ? d_s.buf.as<long long>() : nullptr,
-                     unsat ? d_u.buf.as<int32_t>() : nullptr, n_inner, status ? d_st.buf.as<int32_t>() : nullptr,
-                     n_outer, nframes, info_len, d_pay.as<uint8_t>(), d_fl.as<uint8_t>(), d_c.as<int32_t>(),
-                     fields ? d_f.as<long long>() : nullptr, nullptr);
-  down(payload, d_pay, nframes * info_len);
-  down(flags, d_fl, nframes * 4);
-  down(corrected, d_c, nframes * 4);
-  if (fields) down(fields, d_f, nframes * 40);
+  frame_unpack_batch(sch, d_in.as<uint8_t>(), in_stride, in_bytes, d_s.opt<long long>(), d_u.opt<int32_t>(), n_inner,
+                     d_st.opt<int32_t>(), n_outer, nframes, info_len, d_pay.as<uint8_t>(), d_fl.as<uint8_t>(),
+                     d_c.as<int32_t>(), fields ? d_f.as<long long>() : nullptr, nullptr);
+  stage_out(payload, d_pay, nframes * info_len);
+  stage_out(flags, d_fl, nframes * 4);
+  stage_out(corrected, d_c, nframes * 4);
+  stage_out(fields, d_f, nframes * 40);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -614,11 +594,11 @@ void frame_coded_bits_batch_host(const frame::Scheme& sch, const uint8_t* in, si
                                  const long long* seeds, size_t nframes, size_t out_len, uint8_t* out) {
   row_geom(sch, in_stride, nbits, out_len, nframes);
   if (nframes == 0) return;
-  Up d_in(in, nframes * in_stride), d_s(seeds, seeds ? nframes * 8 : 0);
+  StagedIn d_in(in, nframes * in_stride), d_s(seeds, seeds ? nframes * 8 : 0);
   DevBuf d_out(nframes * out_len + 16);
-  frame_coded_bits_batch(sch, d_in.buf.as<uint8_t>(), in_stride, nbits, seeds ? d_s.buf.as<long long>() : nullptr,
-                         nframes, out_len, d_out.as<uint8_t>(), nullptr);
-  down(out, d_out, nframes * out_len);
+  frame_coded_bits_batch(sch, d_in.as<uint8_t>(), in_stride, nbits, d_s.opt<long long>(), nframes, out_len,
+                         d_out.as<uint8_t>(), nullptr);
+  stage_out(out, d_out, nframes * out_len);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -626,11 +606,11 @@ void frame_llr_prepare_batch_host(const frame::Scheme& sch, const float* in, siz
                                   const long long* seeds, size_t nframes, float* out) {
   row_geom(sch, in_stride, n, n, nframes);
   if (nframes == 0) return;
-  Up d_in(in, nframes * in_stride * 4), d_s(seeds, seeds ? nframes * 8 : 0);
+  StagedIn d_in(in, nframes * in_stride * 4), d_s(seeds, seeds ? nframes * 8 : 0);
   DevBuf d_out(nframes * n * 4 + 16);
-  frame_llr_prepare_batch(sch, d_in.buf.as<float>(), in_stride, n, seeds ? d_s.buf.as<long long>() : nullptr, nframes,
-                          d_out.as<float>(), nullptr);
-  down(out, d_out, nframes * n * 4);
+  frame_llr_prepare_batch(sch, d_in.as<float>(), in_stride, n, d_s.opt<long long>(), nframes, d_out.as<float>(),
+                          nullptr);
+  stage_out(out, d_out, nframes * n * 4);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -638,10 +618,10 @@ void frame_bytes_to_bits_batch_host(const uint8_t* in, size_t nframes, size_t nb
   if (nframes > kFrameMaxFrames || nbytes > kFrameMaxRow || nframes * nbytes > (size_t(1) << 36))
     throw std::invalid_argument("frame: nframes above 2^24, rows above 2^24 bytes or more than 2^36 bytes");
   if (nframes * nbytes == 0) return;
-  Up d_in(in, nframes * nbytes);
+  StagedIn d_in(in, nframes * nbytes);
   DevBuf d_out(nframes * nbytes * 8 + 16);
-  frame_bytes_to_bits_batch(d_in.buf.as<uint8_t>(), nframes, nbytes, d_out.as<uint8_t>(), nullptr);
-  down(out, d_out, nframes * nbytes * 8);
+  frame_bytes_to_bits_batch(d_in.as<uint8_t>(), nframes, nbytes, d_out.as<uint8_t>(), nullptr);
+  stage_out(out, d_out, nframes * nbytes * 8);
   ORION_HIP(hipDeviceSynchronize());
 }
 

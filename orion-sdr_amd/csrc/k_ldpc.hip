@@ -15,7 +15,7 @@
 // order, every * and + is its own rounding (-ffp-contract=off, no FMA here), / is the
 // IEEE divide, and the comparisons are the reference's own (NaN and +-inf behave as on
 // the host).
-#include "hip_common.hpp"
+#include "code_dev.hpp"
 #include "kernels.hpp"
 #include "ldpc.hpp"
 
@@ -23,22 +23,6 @@ namespace orion {
 
 namespace {
 __device__ const ldpc::Packed kTab = ldpc::make_packed();
-
-// ldpc.rs:644-663
-__device__ __forceinline__ float fast_tanh(float x) {
-  if (x < -4.97f) return -1.0f;
-  if (x > 4.97f) return 1.0f;
-  const float x2 = x * x;
-  const float a = x * (945.0f + x2 * (105.0f + x2));
-  const float b = 945.0f + x2 * (420.0f + x2 * 15.0f);
-  return a / b;
-}
-__device__ __forceinline__ float fast_atanh(float x) {
-  const float x2 = x * x;
-  const float a = x * (945.0f + x2 * (-735.0f + x2 * 64.0f));
-  const float b = 945.0f + x2 * (-1050.0f + x2 * 225.0f);
-  return a / b;
-}
 
 // The hard decisions of a codeword: bit i is bit (i & 63) of w[i >> 6]; wave-uniform.
 struct Word {

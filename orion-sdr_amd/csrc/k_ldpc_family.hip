@@ -30,8 +30,8 @@
 #include <mutex>
 #include <vector>
 
+#include "code_dev.hpp"
 #include "fec.hpp"
-#include "hip_common.hpp"
 #include "ldpc_family_blocks.hpp"
 
 namespace orion {
@@ -46,22 +46,6 @@ struct LdpcfGeom {
   int32_t max_iter;
   float scale;
 };
-
-// ldpc_codes.rs:560-580
-__device__ __forceinline__ float lf_tanh(float x) {
-  if (x < -4.97f) return -1.0f;
-  if (x > 4.97f) return 1.0f;
-  const float x2 = x * x;
-  const float a = x * (945.0f + x2 * (105.0f + x2));
-  const float b = 945.0f + x2 * (420.0f + x2 * 15.0f);
-  return a / b;
-}
-__device__ __forceinline__ float lf_atanh(float x) {
-  const float x2 = x * x;
-  const float a = x * (945.0f + x2 * (-735.0f + x2 * 64.0f));
-  const float b = 945.0f + x2 * (-1050.0f + x2 * 225.0f);
-  return a / b;
-}
 
 // The code's table, u32 words: per bit b words 2 b, 2 b + 1 = e0 | e1 << 16, e2 | degree << 16
 // (the bit's edges in ascending check order); per check c word 2 N + c = first edge | degree <<
@@ -114,9 +98,9 @@ __global__ __launch_bounds__(64) void k_ldpcf_decode(const float* __restrict__ l
     bd1[q] = tab[2u * b + 1u];
     const uint32_t p = blk * N + b;
     uint32_t src = p;
-    if (g.block) {  // uniform; out[r cols + c] = in[c rows + r], every block is whole
-      const uint32_t b0 = p / g.block * g.block, o = p - b0, r = o / g.cols, c = o - r * g.cols;
-      src = b0 + c * g.rows + r;
+    if (g.block) {  // uniform; every block is whole
+      const uint32_t b0 = p / g.block * g.block;
+      src = b0 + block_il_offset(p - b0, g.rows, g.cols);
     }
     lv[q] = L[src];
   }
@@ -157,7 +141,7 @@ __global__ __launch_bounds__(64) void k_ldpcf_decode(const float* __restrict__ l
         if (SP) {
           float th[MAXDEG];
 #pragma unroll
-          for (int j = 0; j < MAXDEG; ++j) th[j] = j < deg ? lf_tanh(s_msg[st + j] / 2.0f) : 1.0f;
+          for (int j = 0; j < MAXDEG; ++j) th[j] = j < deg ? fast_tanh(s_msg[st + j] / 2.0f) : 1.0f;
 #pragma unroll
           for (int i1 = 0; i1 < MAXDEG; ++i1) {
             float prod = 1.0f;
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(64) void k_ldpcf_decode(const float* __restrict__ l
               if (i2 != i1) prod *= th[i2];
             if (prod < -1.0f) prod = -1.0f;  // f32::clamp: NaN passes
             if (prod > 1.0f) prod = 1.0f;
-            if (i1 < deg) s_msg[st + i1] = 2.0f * lf_atanh(prod);
+            if (i1 < deg) s_msg[st + i1] = 2.0f * fast_atanh(prod);
           }
         } else {
           float v[MAXDEG];
@@ -266,8 +250,8 @@ __global__ __launch_bounds__(64) void k_ldpcf_encode(const uint8_t* __restrict__
   uint8_t* O = out + static_cast<uint64_t>(stream) * g.out_len;
   auto dst = [&](uint32_t p) {
     if (!g.block) return p;
-    const uint32_t b0 = p / g.block * g.block, o = p - b0, r = o / g.cols, c = o - r * g.cols;
-    return b0 + c * g.rows + r;
+    const uint32_t b0 = p / g.block * g.block;
+    return b0 + block_il_offset(p - b0, g.rows, g.cols);
   };
   if (lane < NW) s_w[lane] = 0u;
   lds_barrier();
@@ -426,13 +410,13 @@ void ldpcf_decode_batch_host(int code, const float* llr, size_t nstreams, size_t
   if (nstreams == 0) return;
   const size_t lb = nstreams * n_llr * sizeof(float), bb = nstreams * nblocks * ldpcf::Ldpc::get(code).k(),
                sb = nstreams * nblocks * sizeof(int32_t);
-  DevBuf d_llr(lb + 16), d_bits(bb + 16), d_unsat(sb), d_iters(sb);
-  ORION_HIP(hipMemcpy(d_llr.as<void>(), llr, lb, hipMemcpyHostToDevice));
+  StagedIn d_llr(llr, lb);
+  DevBuf d_bits(bb + 16), d_unsat(sb), d_iters(sb);
   ldpcf_decode_batch(code, d_llr.as<float>(), nstreams, n_llr, rows, cols, max_iter, rule, scale, d_bits.as<uint8_t>(),
                      d_unsat.as<int32_t>(), d_iters.as<int32_t>(), nullptr);
-  ORION_HIP(hipMemcpy(bits, d_bits.as<void>(), bb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(unsat, d_unsat.as<void>(), sb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(iterations, d_iters.as<void>(), sb, hipMemcpyDeviceToHost));
+  stage_out(bits, d_bits, bb);
+  stage_out(unsat, d_unsat, sb);
+  stage_out(iterations, d_iters, sb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -473,10 +457,10 @@ void ldpcf_encode_batch_host(int code, const uint8_t* bits, size_t nstreams, siz
   if (nstreams > kLdpcfMaxStreams) throw std::invalid_argument("ldpc family: nstreams above 2^24");
   if (nstreams == 0) return;
   const size_t ib = nstreams * nbits, ob = nstreams * out_len;
-  DevBuf d_in(ib + 16), d_out(ob + 16);
-  ORION_HIP(hipMemcpy(d_in.as<void>(), bits, ib, hipMemcpyHostToDevice));
+  StagedIn d_in(bits, ib);
+  DevBuf d_out(ob + 16);
   ldpcf_encode_batch(code, d_in.as<uint8_t>(), nstreams, nbits, rows, cols, d_out.as<uint8_t>(), nullptr);
-  ORION_HIP(hipMemcpy(coded, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(coded, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 

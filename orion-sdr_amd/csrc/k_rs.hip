@@ -4,8 +4,8 @@
 // Forney interleaver (fec/interleaver.rs:122-305, modulate/ofdm_frame.rs:464-478).
 //
 // The decode. One wave64 per codeword, kRsWaves codewords per workgroup; the GF(2^8) exp/log
-// tables (rs.hpp make_gf_tables) sit in LDS, as do the word, its syndromes, the locator and
-// the evaluator of each wave. Lane l holds bytes l, l + 64, l + 128, l + 192 of the word. The
+// tables and the wave algebra on them are gf256_wave.hpp's; the tables sit in LDS, as do the
+// word, its syndromes, the locator and the evaluator of each wave. Lane l holds bytes l, l + 64, l + 128, l + 192 of the word. The
 // fetch of a byte fuses the bit packing (eight bytes of one bit each, MSB first; one 8-byte
 // load where the stream is 8-byte aligned) and the frame-mode Forney deinterleaver (payload
 // byte q is stream byte D + q - (I - 1 - q mod I) M I, always inside the stream). Position p
@@ -27,7 +27,7 @@
 // (rs.cpp), and so are the decisions. Every loop is bounded by a launch constant.
 #include <algorithm>
 
-#include "hip_common.hpp"
+#include "gf256_wave.hpp"
 #include "rs_blocks.hpp"
 
 namespace orion {
@@ -36,7 +36,6 @@ namespace {
 constexpr int kRsWaves = 4;  // codewords per workgroup of the decoder
 constexpr int kEncLanes = 32;  // lanes per codeword of the encoder: one per parity cell
 
-__constant__ __attribute__((aligned(16))) rs::GfTables d_gf = rs::make_gf_tables();
 __constant__ __attribute__((aligned(16))) rs::TsDispersalMask d_mask = rs::make_ts_dispersal_mask();
 
 // what a launch's words share; every field is wave-uniform
@@ -46,17 +45,6 @@ struct RsGeom {
   uint32_t bits, aligned8, disperse;
   uint64_t stream_len;  // elements of one input stream
 };
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v ^= __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t gf_mul(const uint8_t* ex, const uint8_t* lg, uint32_t a, uint32_t b) {
-  const uint32_t v = ex[lg[a] + lg[b]];
-  return a != 0 && b != 0 ? v : 0u;
-}
 
 // payload byte q of a stream
 __device__ __forceinline__ uint32_t rs_fetch(const uint8_t* __restrict__ base, const RsGeom& g, uint32_t q) {
@@ -77,41 +65,19 @@ __device__ __forceinline__ uint32_t rs_fetch(const uint8_t* __restrict__ base, c
 }
 
 // The np syndromes of the word whose bytes lane, lane + 64, .. this lane holds in r, four to
-// a word of sw (S_j in byte j % 4 of sw[j / 4]), the same in every lane. Returns their OR.
+// a word of sw (S_j in byte j % 4 of sw[j / 4]), the same in every lane: a byte b at position p
+// starts at exponent log b. Returns their OR.
 __device__ __forceinline__ uint32_t rs_syndromes(const uint8_t* ex, const uint8_t* lg, const uint32_t r[4],
-                                                 uint32_t lane, const RsGeom& g, uint32_t sw[8]) {
-  uint32_t e[4], d[4];
+                                                 uint32_t lane, const RsGeom& g, uint32_t (&sw)[8]) {
+  uint32_t start[4];
   bool nz[4];
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    const uint32_t p = lane + 64u * a;
-    nz[a] = p < g.n && r[a] != 0;
-    e[a] = lg[r[a]];
-    d[a] = p < 255u ? 254u - p : 0u;
+    nz[a] = lane + 64u * a < g.n && r[a] != 0;
+    start[a] = lg[r[a]];
   }
   uint32_t any = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    uint32_t word = 0;
-    if (4u * w < g.np) {  // uniform
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        if (4u * w + jj < g.np) {
-          uint32_t byte = 0;
-#pragma unroll
-          for (int a = 0; a < 4; ++a) {
-            if (nz[a]) byte ^= ex[e[a]];
-            e[a] += d[a];
-            if (e[a] >= 255u) e[a] -= 255u;
-          }
-          word |= byte << (8 * jj);
-        }
-      }
-      word = wave_xor(word);
-    }
-    sw[w] = word;
-    any |= word;
-  }
+  gf256::syndromes(ex, lane, start, nz, g.np, sw, [&](uint32_t word) { any |= word; });
   return any;
 }
 }  // namespace
@@ -119,13 +85,13 @@ __device__ __forceinline__ uint32_t rs_syndromes(const uint8_t* ex, const uint8_
 __global__ __launch_bounds__(64 * kRsWaves) void k_rs_decode(const uint8_t* __restrict__ in, long long total_cw,
                                                             RsGeom g, uint8_t* __restrict__ msgs,
                                                             int32_t* __restrict__ status) {
-  __shared__ uint32_t s_tab[192];  // exp[512] | log[256]
+  __shared__ uint32_t s_tab[gf256::kTableWords];  // exp[512] | log[256]
   __shared__ uint8_t s_word[kRsWaves][256];
   __shared__ uint32_t s_syn[kRsWaves][8];
   __shared__ uint8_t s_sig[kRsWaves][64];
   __shared__ uint8_t s_omg[kRsWaves][32];
   const uint32_t tid = threadIdx.x;
-  if (tid < 192) s_tab[tid] = reinterpret_cast<const uint32_t*>(&d_gf)[tid];
+  gf256::load_tables(s_tab, tid);
   __syncthreads();  // the only workgroup barrier: a wave without a word leaves after it
   const uint8_t* ex = reinterpret_cast<const uint8_t*>(s_tab);
   const uint8_t* lg = ex + 512;
@@ -159,49 +125,19 @@ __global__ __launch_bounds__(64 * kRsWaves) void k_rs_decode(const uint8_t* __re
     }
     wave_lds_fence();
 
-    // Berlekamp-Massey, reed_solomon.rs:286-318; sigma_i and b_i in lane i
-    uint32_t sigma = lane == 0 ? 1u : 0u, bpoly = sigma;
-    uint32_t L = 0, m = 1;
-    for (uint32_t it = 0; it < 2u * g.t; ++it) {
-      uint32_t term = 0;
-      if (lane >= 1 && lane <= L) term = gf_mul(ex, lg, sigma, syn[it - lane]);  // L <= it
-      const uint32_t delta = wave_xor(term) ^ syn[it];
-      if (delta == 0) {
-        ++m;
-      } else {
-        uint32_t sh = __shfl_up(bpoly, m, 64);
-        if (lane < m) sh = 0;
-        const uint32_t next = sigma ^ gf_mul(ex, lg, delta, sh);
-        if (2u * L <= it) {
-          L = it + 1u - L;
-          bpoly = gf_mul(ex, lg, sigma, ex[255u - lg[delta]]);
-          m = 1;
-        } else {
-          ++m;
-        }
-        sigma = next;
-      }
-    }
+    const uint32_t sigma = gf256::berlekamp_massey(ex, lg, syn, lane, 2u * g.t);  // sigma_i in lane i
     const uint64_t nzmask = __ballot(sigma != 0);  // bit 0 is set: sigma_0 = 1
     const uint32_t sigma_deg = 63u - static_cast<uint32_t>(__clzll(static_cast<long long>(nzmask)));
     sig[lane] = static_cast<uint8_t>(sigma);
     wave_lds_fence();
 
-    // Chien, reed_solomon.rs:173-185: sigma(2^-i) = sum sigma_d exp[(log sigma_d + d (255 - i)) mod 255]
+    // Chien, reed_solomon.rs:173-185: the roots are recorded for Forney
     uint32_t nroots = 0;
     bool root[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const uint32_t i = lane + 64u * a;
-      const uint32_t step = (255u - i % 255u) % 255u;
-      uint32_t e = 0, val = 0;
-      for (uint32_t d = 0; d <= 2u * g.t; ++d) {
-        const uint32_t c = sig[d];
-        if (c != 0) val ^= ex[lg[c] + e];
-        e += step;
-        if (e >= 255u) e -= 255u;
-      }
-      root[a] = i < 255u && val == 0;
+      root[a] = i < 255u && gf256::chien(ex, lg, sig, i, 2u * g.t) == 0;
       nroots += static_cast<uint32_t>(__popcll(__ballot(root[a])));
     }
 
@@ -210,7 +146,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void k_rs_decode(const uint8_t* __re
       if (lane < 32) {
         uint32_t o = 0;
         for (uint32_t j = 0; j < g.np; ++j)
-          if (j <= lane && lane < g.np) o ^= gf_mul(ex, lg, syn[lane - j], sig[j]);
+          if (j <= lane && lane < g.np) o ^= gf256::mul(ex, lg, syn[lane - j], sig[j]);
         omg[lane] = static_cast<uint8_t>(o);
       }
       wave_lds_fence();
@@ -287,9 +223,9 @@ struct RsEncGeom {
 // output, 32 bytes at a time.
 __global__ __launch_bounds__(256) void k_rs_encode(const uint8_t* __restrict__ msgs, long long total_cw, RsEncGeom g,
                                                    uint8_t* __restrict__ cws) {
-  __shared__ uint32_t s_tab[192];
+  __shared__ uint32_t s_tab[gf256::kTableWords];
   const uint32_t tid = threadIdx.x;
-  if (tid < 192) s_tab[tid] = reinterpret_cast<const uint32_t*>(&d_gf)[tid];
+  gf256::load_tables(s_tab, tid);
   __syncthreads();
   const uint8_t* ex = reinterpret_cast<const uint8_t*>(s_tab);
   const uint8_t* lg = ex + 512;
@@ -316,7 +252,7 @@ __global__ __launch_bounds__(256) void k_rs_encode(const uint8_t* __restrict__ m
       const uint32_t fb = __shfl(mine, static_cast<int>(j), kEncLanes) ^ __shfl(reg, 0, kEncLanes);
       uint32_t next = __shfl_down(reg, 1, kEncLanes);
       if (li + 1u >= g.np) next = 0;
-      reg = next ^ gf_mul(ex, lg, fb, gc);
+      reg = next ^ gf256::mul(ex, lg, fb, gc);
     }
   }
   if (live && li < g.np) C[g.k + li] = static_cast<uint8_t>(reg);
@@ -406,12 +342,12 @@ void rs_decode_batch_host(size_t n, size_t n_parity, const uint8_t* in, size_t n
   if (nstreams == 0) return;
   const size_t ib = nstreams * (ncw * n + c.delay) * (f.bits ? 8 : 1), mb = nstreams * ncw * c.k,
                sb = nstreams * ncw * sizeof(int32_t);
-  DevBuf d_in(ib + 16), d_msgs(mb + 16), d_status(sb);
-  ORION_HIP(hipMemcpy(d_in.as<void>(), in, ib, hipMemcpyHostToDevice));
+  StagedIn d_in(in, ib);
+  DevBuf d_msgs(mb + 16), d_status(sb);
   rs_decode_batch(n, n_parity, d_in.as<uint8_t>(), nstreams, ncw, f, d_msgs.as<uint8_t>(), d_status.as<int32_t>(),
                   nullptr);
-  ORION_HIP(hipMemcpy(msgs, d_msgs.as<void>(), mb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(status, d_status.as<void>(), sb, hipMemcpyDeviceToHost));
+  stage_out(msgs, d_msgs, mb);
+  stage_out(status, d_status, sb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -440,10 +376,10 @@ void rs_encode_batch_host(size_t n, size_t n_parity, const uint8_t* msgs, size_t
   const RsCheck c = rs_check(n, n_parity, nstreams, ncw, f);
   if (nstreams == 0) return;
   const size_t mb = nstreams * ncw * c.k, cb = nstreams * ncw * n;
-  DevBuf d_msgs(mb + 16), d_cws(cb + 16);
-  ORION_HIP(hipMemcpy(d_msgs.as<void>(), msgs, mb, hipMemcpyHostToDevice));
+  StagedIn d_msgs(msgs, mb);
+  DevBuf d_cws(cb + 16);
   rs_encode_batch(n, n_parity, d_msgs.as<uint8_t>(), nstreams, ncw, f, d_cws.as<uint8_t>(), nullptr);
-  ORION_HIP(hipMemcpy(cws, d_cws.as<void>(), cb, hipMemcpyDeviceToHost));
+  stage_out(cws, d_cws, cb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -485,10 +421,10 @@ void forney_interleave_batch_host(size_t branches, size_t depth, const uint8_t* 
   const ForneyGeom g = forney_geom(branches, depth, nstreams, len, bits);
   if (nstreams == 0) return;
   const size_t ib = nstreams * len, ob = nstreams * g.out_len;
-  DevBuf d_in(ib + 16), d_out(ob + 16);
-  ORION_HIP(hipMemcpy(d_in.as<void>(), in, ib, hipMemcpyHostToDevice));
+  StagedIn d_in(in, ib);
+  DevBuf d_out(ob + 16);
   forney_interleave_batch(branches, depth, d_in.as<uint8_t>(), nstreams, len, bits, d_out.as<uint8_t>(), nullptr);
-  ORION_HIP(hipMemcpy(out, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(out, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 

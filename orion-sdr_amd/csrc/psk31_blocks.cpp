@@ -32,10 +32,10 @@ void psk31_viterbi_host(const float* soft, size_t nstreams, size_t n_syms, uint8
   if (nstreams == 0 || n_syms == 0) return;
   const size_t sb = nstreams * n_syms * 2 * sizeof(float), bb = nstreams * n_syms;
   const size_t wb = psk31::viterbi_work_bytes(nstreams, n_syms);
-  DevBuf d_soft(sb), d_bits(bb + 16), d_work(wb);
-  ORION_HIP(hipMemcpy(d_soft.as<void>(), soft, sb, hipMemcpyHostToDevice));
+  StagedIn d_soft(soft, sb, 0);
+  DevBuf d_bits(bb + 16), d_work(wb);
   psk31_viterbi(d_soft.as<float>(), nstreams, n_syms, d_bits.as<uint8_t>(), d_work.as<void>(), wb, nullptr);
-  ORION_HIP(hipMemcpy(bits, d_bits.as<void>(), bb, hipMemcpyDeviceToHost));
+  stage_out(bits, d_bits, bb);
   ORION_HIP(hipDeviceSynchronize());
 }
 

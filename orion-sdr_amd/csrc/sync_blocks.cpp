@@ -168,13 +168,12 @@ void ldpc_decode_host(const float* llr, size_t n, const uint32_t* count, size_t 
   if (n == 0) return;
   const size_t lb = n * ldpc::kN * sizeof(float), rb = n * sizeof(ldpc::Result), pb = plain ? n * ldpc::kN : 0;
   const size_t nb = count ? n / max_cand * sizeof(uint32_t) : 0;
-  DevBuf d_llr(lb), d_res(rb), d_plain(pb + 16), d_count(nb + 16);
-  ORION_HIP(hipMemcpy(d_llr.as<void>(), llr, lb, hipMemcpyHostToDevice));
-  if (nb) ORION_HIP(hipMemcpy(d_count.as<void>(), count, nb, hipMemcpyHostToDevice));
-  ldpc_decode(d_llr.as<float>(), n, count ? d_count.as<uint32_t>() : nullptr, max_cand, protocol, rule, max_iter,
-              d_res.as<void>(), plain ? d_plain.as<uint8_t>() : nullptr, nullptr);
-  ORION_HIP(hipMemcpy(results, d_res.as<void>(), rb, hipMemcpyDeviceToHost));
-  if (pb) ORION_HIP(hipMemcpy(plain, d_plain.as<void>(), pb, hipMemcpyDeviceToHost));
+  StagedIn d_llr(llr, lb, 0), d_count(count, nb);
+  DevBuf d_res(rb), d_plain(pb + 16);
+  ldpc_decode(d_llr.as<float>(), n, d_count.opt<uint32_t>(), max_cand, protocol, rule, max_iter, d_res.as<void>(),
+              plain ? d_plain.as<uint8_t>() : nullptr, nullptr);
+  stage_out(results, d_res, rb);
+  stage_out(plain, d_plain, pb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -325,12 +324,12 @@ void ft_demod_host(int protocol, float fs, float base_hz, const void* iq, size_t
     throw std::invalid_argument("demodulate: nframes <= 65535, n_per_frame <= 2^40");
   if (nframes == 0) return;
   const size_t ib = nframes * n_per_frame * 8, tb = nframes * m.data, eb = energies ? nframes * m.total * m.tones * 4 : 0;
-  DevBuf d_iq(ib), d_t(tb + 16), d_e(eb + 16);
-  ORION_HIP(hipMemcpy(d_iq.as<void>(), iq, ib, hipMemcpyHostToDevice));
+  StagedIn d_iq(iq, ib, 0);
+  DevBuf d_t(tb + 16), d_e(eb + 16);
   ft_demod(protocol, fs, base_hz, d_iq.as<void>(), nframes, n_per_frame, d_t.as<uint8_t>(),
            energies ? d_e.as<float>() : nullptr, nullptr);
-  ORION_HIP(hipMemcpy(tones, d_t.as<void>(), tb, hipMemcpyDeviceToHost));
-  if (eb) ORION_HIP(hipMemcpy(energies, d_e.as<void>(), eb, hipMemcpyDeviceToHost));
+  stage_out(tones, d_t, tb);
+  stage_out(energies, d_e, eb);
   ORION_HIP(hipDeviceSynchronize());
 }
 

@@ -16,9 +16,12 @@ import numpy as np
 from np_ref_rs import EXP, LOG, gf_inv, gf_mul
 
 # (n, t, errors): the frame's code on both sides of t, the perfect code of t = 1 (two errors
-# always miscorrect), shortened codes, a long locator, the shortest legal word
+# always miscorrect), shortened codes, a long locator, the shortest legal word, and the largest
+# t of the device on both sides of it, full length and shortened: all 62 syndromes live (the
+# last packed word half used) and a locator that reaches lane 32 and beyond
 ROWS = [(184, 8, 0), (184, 8, 1), (184, 8, 4), (184, 8, 8), (184, 8, 9), (184, 8, 12), (255, 1, 2), (255, 2, 2),
-        (255, 2, 3), (128, 3, 3), (128, 3, 4), (255, 16, 16), (255, 16, 17), (9, 1, 0), (9, 1, 1), (9, 1, 2)]
+        (255, 2, 3), (128, 3, 3), (128, 3, 4), (255, 16, 16), (255, 16, 17), (9, 1, 0), (9, 1, 1), (9, 1, 2),
+        (255, 31, 31), (255, 31, 32), (207, 31, 31), (207, 31, 33)]
 SEED = 41
 WORDS = 26  # no multiple of the kernel's four words per workgroup
 
