@@ -1,5 +1,6 @@
 // code_dev.hpp — small device helpers that the code kernels share (k_fec.hip, k_ldpc.hip,
-// k_ldpc_family.hip).
+// k_ldpc_family.hip). The Viterbi engine that k_fec.hip shares with k_psk31.hip is
+// trellis_wave.hpp, the GF(2^8) algebra of k_rs.hip and k_bch.hip gf256_wave.hpp.
 #pragma once
 #include "hip_common.hpp"
 

@@ -13,6 +13,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "trellis.hpp"
+
 namespace orion {
 namespace fec {
 
@@ -79,12 +81,10 @@ class BlockInterleaver {
   size_t rows_, cols_;
 };
 
-// Bytes of device scratch k_conv_viterbi needs (k_fec.hip): per step and stream the two
-// ballots "the higher predecessor won" and "a predecessor was taken", [step][stream]. K = 5:
-// one uint32 (16 + 16 bits), streams rounded up to the four of a wave. K = 7: two uint64.
+// Bytes of device scratch k_conv_viterbi needs (k_fec.hip): the survivor words of the
+// info_bits + reg_bits steps (trellis.hpp).
 inline size_t viterbi_work_bytes(int reg_bits, size_t nstreams, size_t info_bits) {
-  const size_t n_steps = info_bits + static_cast<size_t>(reg_bits);
-  return reg_bits == 4 ? (nstreams + 3) / 4 * 4 * n_steps * 4 : nstreams * n_steps * 16;
+  return trellis::work_bytes(reg_bits, nstreams, info_bits + static_cast<size_t>(reg_bits));
 }
 
 }  // namespace fec

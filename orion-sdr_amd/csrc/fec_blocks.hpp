@@ -1,6 +1,7 @@
 // fec_blocks.hpp — the inner code on the device (k_fec.hip): the batched soft Viterbi decode
-// with depuncturing and block deinterleaving fused into its LLR fetch, and the batched
-// encoder with puncturing and block interleaving. The scalar code they are held to is fec.hpp.
+// (the wave engine of trellis_wave.hpp) with depuncturing and block deinterleaving fused into
+// its LLR fetch, and the batched encoder with puncturing and block interleaving. The scalar
+// code they are held to is fec.hpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>

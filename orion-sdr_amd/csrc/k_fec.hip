@@ -3,43 +3,30 @@
 // viterbi_decode_soft_with; K = 5 and DVB-T's K = 7), and the batched encoder
 // (conv.rs:234-263) with the block interleaver of the frame chain on either side.
 //
-// The Viterbi decode. One lane per trellis state: K = 7 has 64 states, one stream per wave64
-// workgroup; K = 5 has 16, four streams per wave. State ns is reached from the two states
-// (ns << 1) & mask and that + 1 with input bit ns >> (K - 2) (next_state, conv.rs:150-152), so
-// a step is two lane shuffles of the path metric, the four correlations of the step's LLR
-// pair (uniform over the stream), a per-lane constant choice of the correlation of each of
-// the lane's two branches, and the compare-select. The LLRs are fetched cooperatively: a
-// group is W / 2 steps (W lanes per stream), lane i of the stream loads mother position
-// 2 t0 + i of the group, one group ahead of the metric chain (the addresses do not depend
-// on it), and a step broadcasts its pair with two more shuffles. That fetch fuses the
-// depuncturing and the deinterleaving: the punctured index of a mother position is full
-// periods times kept-per-period plus a prefix count inside the period; a deleted position,
-// and an index at or past the coded length or n_llr, reads as 0.0; the index goes through
-// the inverse block permutation in[b R C + c R + r] where its block lies wholly inside
-// n_llr, and is itself in a short last chunk (deinterleave_llrs, demodulate/ofdm_frame.rs).
-// Each step leaves two ballots per stream in the scratch array (fec.hpp viterbi_work_bytes):
-// the higher predecessor won, and a predecessor was taken at all. Lane 0 of the stream then
-// runs the traceback from state 0 over those words, reading eight ahead of the chain of states.
-//
-// Bit-exactness with the host decoder (fec.cpp) and the reference: the start metric is
-// f32::MIN / 2 with state 0 at 0; a predecessor whose metric is <= that value is skipped;
-// the candidate is pm + corr, one rounding, with corr one of l0 + l1, l0 - l1, -l0 + l1,
-// -l0 - l1 (-ffp-contract=off); the reference visits states ascending and replaces a
-// survivor on strict > only, which for one next state is: the lower predecessor first, against
-// f32::MIN / 2, then the higher one against the result; a survivor entry that nobody wrote
-// reads as state 0, as the reference's zeroed table does (what NaN input, or metrics at
-// -inf, lead to: the comparisons are the reference's own, so such input gives the host's
-// bits too). Every loop is bounded by n_steps.
+// The Viterbi decode is trellis_wave.hpp's engine (one lane per state: K = 7 is one stream per
+// wave64 workgroup, K = 5 four; the exactness argument is there), maximising. What is this
+// kernel's: the branch metric is one of the four correlations l0 + l1, l0 - l1, -l0 + l1,
+// -l0 - l1 of the step's LLR pair (uniform over the stream; negation is exact,
+// -ffp-contract=off), a per-lane constant choice for each of the lane's two branches. The LLRs
+// are fetched cooperatively: a group is W / 2 steps (W lanes per stream), lane i of the
+// stream loads mother position 2 t0 + i of the group, one group ahead of the metric chain
+// (the addresses do not depend on it), and a step broadcasts its pair with two shuffles.
+// That fetch fuses the depuncturing and the deinterleaving: the punctured index of a mother
+// position is full periods times kept-per-period plus a prefix count inside the period; a
+// deleted position, and an index at or past the coded length or n_llr, reads as 0.0; the
+// index goes through the inverse block permutation in[b R C + c R + r] where its block lies
+// wholly inside n_llr, and is itself in a short last chunk (deinterleave_llrs,
+// demodulate/ofdm_frame.rs). The traceback starts from state 0 (the zero tail) and writes
+// the first info_bits bits of the n_steps <= 2^24 + 6.
 #include <algorithm>
 
 #include "code_dev.hpp"
 #include "fec_blocks.hpp"
+#include "trellis_wave.hpp"
 
 namespace orion {
 
 namespace {
-constexpr int kTraceAhead = 8;  // survivor words fetched ahead of the traceback's chain of states
-
 // what a launch's streams share; every field is wave-uniform
 struct FecGeom {
   uint32_t n_steps, info_bits, n_llr;
@@ -49,8 +36,6 @@ struct FecGeom {
   uint32_t rows, cols, block;  // block = rows * cols, 0: no interleaver
   uint32_t g0, g1;
 };
-
-__device__ __forceinline__ uint32_t fec_parity(uint32_t x) { return static_cast<uint32_t>(__popc(x)) & 1u; }
 
 // The LLR of mother position 2 (full * period + col) + j of a stream: 0.0 unless the bit was
 // kept and its punctured index lies inside lim.
@@ -71,37 +56,26 @@ __device__ __forceinline__ float fec_fetch(const float* __restrict__ L, const Fe
 
 template <int RB>
 __global__ __launch_bounds__(64) void k_conv_viterbi(const float* __restrict__ llr, long long nstreams, FecGeom g,
-                                                     uint8_t* __restrict__ bits, void* __restrict__ work_v) {
-  constexpr int W = 1 << RB;   // states: lanes per stream
-  constexpr int SPW = 64 / W;  // streams per wave
-  constexpr int H = W / 2;     // steps per fetch group
-  const float kNegInf = -3.4028234663852886e38f / 2.0f;  // f32::MIN / 2, conv.rs:343
-  const int lane = threadIdx.x;
-  const int st = lane & (W - 1), gshift = lane & (64 - W);
-  const long long nsr = (nstreams + SPW - 1) / SPW * SPW;
-  const long long stream = static_cast<long long>(blockIdx.x) * SPW + (lane >> RB);
-  const bool live = stream < nstreams;
-  // a group past the last stream runs the last stream's arithmetic (the shuffles and ballots
-  // are wave-wide) and stores nothing
-  const float* L = llr + (live ? stream : nstreams - 1) * static_cast<long long>(g.n_llr);
-  uint32_t* work32 = static_cast<uint32_t*>(work_v);
-  uint64_t* work64 = static_cast<uint64_t*>(work_v);
+                                                     uint8_t* __restrict__ bits, void* __restrict__ work) {
+  using trellis::parity;
+  constexpr int W = 1 << RB, H = W / 2;  // lanes per stream; steps per fetch group
+  const trellis::Wave<RB> tw(nstreams);
+  const uint32_t st = static_cast<uint32_t>(tw.st);
+  const float* L = llr + tw.row * static_cast<long long>(g.n_llr);
 
-  // this state's two predecessors and the coded pair (c0 << 1 | c1) of their branches
-  const int p0 = (st << 1) & (W - 1);
-  const uint32_t inbit = static_cast<uint32_t>(st) >> (RB - 1);
-  const uint32_t w0 = inbit << RB | static_cast<uint32_t>(p0);
-  const uint32_t sym0 = fec_parity(w0 & g.g0) << 1 | fec_parity(w0 & g.g1);
-  const uint32_t sym1 = fec_parity((w0 + 1u) & g.g0) << 1 | fec_parity((w0 + 1u) & g.g1);
+  // the coded pair (c0 << 1 | c1) of the branches from this state's two predecessors
+  const uint32_t w0 = tw.inbit << RB | static_cast<uint32_t>(tw.p0);
+  const uint32_t sym0 = parity(w0 & g.g0) << 1 | parity(w0 & g.g1);
+  const uint32_t sym1 = parity((w0 + 1u) & g.g0) << 1 | parity((w0 + 1u) & g.g1);
 
   // this lane's mother position in the group, as (full periods, column, generator); a group on, the
   // step count grows by H
-  const uint32_t j = static_cast<uint32_t>(st) & 1u;
-  uint32_t full = (static_cast<uint32_t>(st) >> 1) / g.period;
-  uint32_t col = (static_cast<uint32_t>(st) >> 1) - full * g.period;
+  const uint32_t j = st & 1u;
+  uint32_t full = (st >> 1) / g.period;
+  uint32_t col = (st >> 1) - full * g.period;
   const uint32_t dfull = static_cast<uint32_t>(H) / g.period, dcol = static_cast<uint32_t>(H) - dfull * g.period;
 
-  float pm = st == 0 ? 0.0f : kNegInf;
+  float pm = st == 0 ? 0.0f : trellis::Maximise::start();
   float cur = fec_fetch(L, g, full, col, j);
   for (uint32_t t0 = 0; t0 < g.n_steps; t0 += H) {
     full += dfull;
@@ -120,74 +94,13 @@ __global__ __launch_bounds__(64) void k_conv_viterbi(const float* __restrict__ l
         const float c0 = l0 + l1, c1 = l0 - l1, c2 = n0 + l1, c3 = n0 - l1;  // conv.rs:363
         const float ca = sym0 & 2u ? (sym0 & 1u ? c3 : c2) : (sym0 & 1u ? c1 : c0);
         const float cb = sym1 & 2u ? (sym1 & 1u ? c3 : c2) : (sym1 & 1u ? c1 : c0);
-        const float pm0 = __shfl(pm, p0, W), pm1 = __shfl(pm, p0 + 1, W);
-        float v = kNegInf;
-        bool taken = false, upper = false;
-        if (!(pm0 <= kNegInf)) {
-          const float cand = pm0 + ca;
-          if (cand > v) {
-            v = cand;
-            taken = true;
-          }
-        }
-        if (!(pm1 <= kNegInf)) {
-          const float cand = pm1 + cb;
-          if (cand > v) {
-            v = cand;
-            taken = true;
-            upper = true;
-          }
-        }
-        pm = v;
-        const uint64_t mu = __ballot(upper), mt = __ballot(taken);
-        if (live && st == 0) {
-          const long long at = static_cast<long long>(t0 + k) * nsr + stream;
-          if constexpr (RB == 4) {
-            work32[at] = static_cast<uint32_t>((mu >> gshift) & 0xFFFFu) |
-                         static_cast<uint32_t>((mt >> gshift) & 0xFFFFu) << 16;
-          } else {
-            work64[2 * at] = mu;
-            work64[2 * at + 1] = mt;
-          }
-        }
+        tw.store(work, static_cast<long long>(t0 + k), tw.template acs<trellis::Maximise>(pm, ca, cb));
       }
     }
     cur = nxt;
   }
-  if (!live || st != 0) return;
-
-  // conv.rs:385-397: from state 0; the same lane wrote these words, so its own program
-  // order suffices
-  uint8_t* B = bits + stream * static_cast<long long>(g.info_bits);
-  uint32_t state = 0;
-  for (long long t1 = g.n_steps; t1 > 0; t1 -= kTraceAhead) {
-    uint64_t wu[kTraceAhead], wt[kTraceAhead];
-#pragma unroll
-    for (int k = 0; k < kTraceAhead; ++k) {
-      const long long t = t1 - 1 - k;
-      wu[k] = 0;
-      wt[k] = 0;
-      if (t >= 0) {
-        const long long at = t * nsr + stream;
-        if constexpr (RB == 4) {
-          const uint32_t w = work32[at];
-          wu[k] = w & 0xFFFFu;
-          wt[k] = w >> 16;
-        } else {
-          wu[k] = work64[2 * at];
-          wt[k] = work64[2 * at + 1];
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kTraceAhead; ++k) {
-      const long long t = t1 - 1 - k;
-      if (t >= 0) {
-        if (t < static_cast<long long>(g.info_bits)) B[t] = static_cast<uint8_t>(state >> (RB - 1) & 1u);
-        state = (wt[k] >> state) & 1u ? ((state << 1) & (W - 1)) | static_cast<uint32_t>((wu[k] >> state) & 1u) : 0u;
-      }
-    }
-  }
+  // conv.rs:385-397
+  tw.traceback(work, g.n_steps, 0u, bits + tw.stream * static_cast<long long>(g.info_bits), g.info_bits);
 }
 
 // One thread per output bit of a stream's interleave_bits(conv_encode_punctured(info)): the
@@ -221,7 +134,7 @@ __global__ __launch_bounds__(256) void k_conv_encode(const uint8_t* __restrict__
       const long long ti = t - RB + i;
       if (ti >= 0 && ti < static_cast<long long>(g.info_bits)) window |= static_cast<uint32_t>(I[ti] & 1u) << i;
     }
-    v = static_cast<uint8_t>(fec_parity(window & (pos & 1u ? g.g1 : g.g0)));
+    v = static_cast<uint8_t>(trellis::parity(window & (pos & 1u ? g.g1 : g.g0)));
   }
   out[idx] = v;
 }

@@ -2,61 +2,41 @@
 // K = 5 convolutional code (codec/psk31.rs:95-160, viterbi_decode), and the demodulator bank
 // (demodulate/psk31.rs, further down).
 //
-// The Viterbi decode. Sixteen lanes per stream, one per trellis state; four streams per wave64 workgroup. State
-// s is reached from the two states 2 (s & 7) and 2 (s & 7) + 1 with input bit s >> 3
-// (next_state, psk31.rs:70-72), so a step is two 16-wide lane shuffles of the path metric, two
-// branch metrics and the compare-select. The soft values are fetched eight symbols ahead of
-// the metric chain (their addresses do not depend on it). Each step leaves one uint32 per
-// stream in the scratch array (psk31.hpp viterbi_work_bytes), built from two ballots: which
-// predecessor won, and whether one was taken at all. Lane 0 of the stream then runs the
-// traceback over those words, again reading eight ahead of the chain of states.
-//
-// Bit-exactness with the host decoder (psk31.cpp) and the reference: the start metric is
-// f32::MAX / 2 with state 0 at 0; a predecessor whose metric is >= that value is skipped; the
-// lower predecessor is tried first and the higher one replaces it only on strict <; the
-// branch metric is (s0 - e0) * (s0 - e0) + (s1 - e1) * (s1 - e1) with every * and + its own
-// rounding (-ffp-contract=off); the first minimum wins the final-state search; a survivor
-// entry that no predecessor wrote reads as state 0, as the reference's zeroed table does
-// (this is what NaN input or metrics at the start value lead to: the comparisons are the
-// reference's own, so such input gives the host's bits too, and every loop is bounded).
+// The Viterbi decode is trellis_wave.hpp's engine (sixteen lanes per stream, four streams per
+// wave64 workgroup; the exactness argument is there), minimising. What is this kernel's: every
+// lane fetches the stream's soft values eight symbols ahead of the metric chain (their
+// addresses do not depend on it); the branch metric is (s0 - e0) * (s0 - e0) + (s1 - e1) *
+// (s1 - e1) against the branch's expected phasor, every * and + its own rounding
+// (-ffp-contract=off); the first minimum wins the final-state search; all n_syms bits are written.
 #include "hip_common.hpp"
 #include "kernels.hpp"
 #include "psk31.hpp"
+#include "trellis_wave.hpp"
 
 namespace orion {
 
 namespace {
-constexpr int kVitAhead = 8;  // symbols (and survivor words) fetched ahead of the dependent chain
+constexpr int kVitAhead = 8;  // symbols fetched ahead of the dependent chain
 constexpr int kDemodAhead = 8;  // samples (and window values) the bank fetches ahead of its chains
-
-__device__ __forceinline__ int psk31_parity(int x) { return __popc(static_cast<unsigned>(x)) & 1; }
 }  // namespace
 
 __global__ __launch_bounds__(64) void k_psk31_viterbi(const float* __restrict__ soft, long long nstreams,
                                                       long long n_syms, uint8_t* __restrict__ bits,
                                                       uint32_t* __restrict__ work) {
-  const float kInf = 3.4028234663852886e38f / 2.0f;  // f32::MAX / 2, psk31.rs:102
-  const int lane = threadIdx.x;
-  const int st = lane & 15, gshift = lane & 48;
-  const long long ns4 = (nstreams + 3) / 4 * 4;
-  const long long stream = static_cast<long long>(blockIdx.x) * 4 + (lane >> 4);
-  const bool live = stream < nstreams;
-  // a group past the last stream runs the last stream's arithmetic (the shuffles and ballots
-  // are wave-wide) and stores nothing
-  const float* S = soft + (live ? stream : nstreams - 1) * 2 * n_syms;
+  const trellis::Wave<4> tw(nstreams);
+  const float* S = soft + tw.row * 2 * n_syms;
 
-  // this state's two predecessors and the expected phasors of their branches (psk31.rs:63-85)
-  const int p0 = (st & 7) << 1, bit = st >> 3;
+  // the expected phasors of the branches from this state's two predecessors (psk31.rs:63-85)
   float e[2][2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const int window = bit << 4 | (p0 + k);
-    const int dibit = psk31_parity(window & 0x15) * 2 + psk31_parity(window & 0x13);
+    const uint32_t window = tw.inbit << 4 | static_cast<uint32_t>(tw.p0 + k);
+    const uint32_t dibit = trellis::parity(window & 0x15) * 2 + trellis::parity(window & 0x13);
     e[k][0] = dibit == 0 ? 1.0f : (dibit == 3 ? -1.0f : 0.0f);
     e[k][1] = dibit == 2 ? 1.0f : (dibit == 1 ? -1.0f : 0.0f);
   }
 
-  float pm = st == 0 ? 0.0f : kInf;
+  float pm = tw.st == 0 ? 0.0f : trellis::Minimise::start();
   float cur[2 * kVitAhead], nxt[2 * kVitAhead];
 #pragma unroll
   for (int k = 0; k < 2 * kVitAhead; ++k) cur[k] = k < 2 * n_syms ? S[k] : 0.0f;
@@ -71,31 +51,9 @@ __global__ __launch_bounds__(64) void k_psk31_viterbi(const float* __restrict__ 
     for (int k = 0; k < kVitAhead; ++k) {
       if (t0 + k < n_syms) {  // uniform over the wave
         const float s0 = cur[2 * k], s1 = cur[2 * k + 1];
-        const float pm0 = __shfl(pm, p0, 16), pm1 = __shfl(pm, p0 + 1, 16);
-        float v = kInf;
-        bool taken = false, upper = false;
-        if (!(pm0 >= kInf)) {
-          const float bm = (s0 - e[0][0]) * (s0 - e[0][0]) + (s1 - e[0][1]) * (s1 - e[0][1]);
-          const float cand = pm0 + bm;
-          if (cand < v) {
-            v = cand;
-            taken = true;
-          }
-        }
-        if (!(pm1 >= kInf)) {
-          const float bm = (s0 - e[1][0]) * (s0 - e[1][0]) + (s1 - e[1][1]) * (s1 - e[1][1]);
-          const float cand = pm1 + bm;
-          if (cand < v) {
-            v = cand;
-            taken = true;
-            upper = true;
-          }
-        }
-        pm = v;
-        const uint64_t mu = __ballot(upper), mt = __ballot(taken);
-        const uint32_t word = static_cast<uint32_t>((mu >> gshift) & 0xFFFFu) |
-                              static_cast<uint32_t>((mt >> gshift) & 0xFFFFu) << 16;
-        if (live && st == 0) work[(t0 + k) * ns4 + stream] = word;
+        const float bm0 = (s0 - e[0][0]) * (s0 - e[0][0]) + (s1 - e[0][1]) * (s1 - e[0][1]);
+        const float bm1 = (s0 - e[1][0]) * (s0 - e[1][0]) + (s1 - e[1][1]) * (s1 - e[1][1]);
+        tw.store(work, t0 + k, tw.acs<trellis::Minimise>(pm, bm0, bm1));
       }
     }
 #pragma unroll
@@ -103,7 +61,7 @@ __global__ __launch_bounds__(64) void k_psk31_viterbi(const float* __restrict__ 
   }
 
   // psk31.rs:139-144: min_by keeps the first of equal minima (and the earlier of an unordered pair)
-  int best = 0;
+  uint32_t best = 0;
   float best_pm = __shfl(pm, 0, 16);
 #pragma unroll
   for (int i = 1; i < 16; ++i) {
@@ -113,23 +71,7 @@ __global__ __launch_bounds__(64) void k_psk31_viterbi(const float* __restrict__ 
       best = i;
     }
   }
-  if (!live || st != 0) return;
-
-  // psk31.rs:147-157: the same lane wrote these words, so its own program order suffices
-  uint8_t* B = bits + stream * n_syms;
-  int state = best;
-  for (long long t1 = n_syms; t1 > 0; t1 -= kVitAhead) {
-    uint32_t w[kVitAhead];
-#pragma unroll
-    for (int k = 0; k < kVitAhead; ++k) w[k] = t1 - 1 - k >= 0 ? work[(t1 - 1 - k) * ns4 + stream] : 0u;
-#pragma unroll
-    for (int k = 0; k < kVitAhead; ++k) {
-      if (t1 - 1 - k >= 0) {
-        B[t1 - 1 - k] = static_cast<uint8_t>((state >> 3) & 1);
-        state = (w[k] >> (16 + state)) & 1u ? ((state & 7) << 1 | static_cast<int>((w[k] >> state) & 1u)) : 0;
-      }
-    }
-  }
+  tw.traceback(work, n_syms, best, bits + tw.stream * n_syms, n_syms);  // psk31.rs:147-157
 }
 
 // ---- the demodulator bank ------------------------------------------------------------------

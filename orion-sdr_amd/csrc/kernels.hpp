@@ -239,7 +239,8 @@ void launch_ft_demod(bool ft4, const f2* x_dev, int nframes, long long n, const 
 // ------------------------------------- PSK31 channel code: batched Viterbi (k_psk31.hip) --
 // viterbi_decode (codec/psk31.rs:95-160) of nstreams soft streams: soft_dev [nstreams][2 *
 // n_syms] f32 -> bits_dev [nstreams][n_syms] u8. work_dev: psk31::viterbi_work_bytes bytes of
-// scratch, 4-byte aligned. nstreams <= 2^31 - 4, n_syms <= 2^31 - 1.
+// scratch (the survivor words of trellis_wave.hpp), 4-byte aligned. nstreams <= 2^31 - 4,
+// n_syms <= 2^31 - 1.
 void launch_psk31_viterbi(const float* soft_dev, long long nstreams, long long n_syms, uint8_t* bits_dev,
                           uint32_t* work_dev, hipStream_t s);
 // The demodulator bank: one launch advances nstreams demodulators over x_dev [nch][n] cf32,

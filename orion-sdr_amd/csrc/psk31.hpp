@@ -16,6 +16,8 @@
 #include <deque>
 #include <vector>
 
+#include "trellis.hpp"
+
 namespace orion {
 namespace psk31 {
 
@@ -244,11 +246,8 @@ size_t sync_num_bins(float base_hz, float max_hz);
 std::vector<Carrier> find_carriers(const float* wf, size_t num_syms, size_t num_bins, size_t min_carrier_syms,
                                    float peak_margin_db, size_t max_cand);
 
-// ---- the batched decode's survivor words (k_psk31.hip) ---------------------------------
-// One uint32 per stream and step: bit s says which of state s's two predecessors won (0:
-// 2 (s & 7), 1: 2 (s & 7) + 1), bit 16 + s that one of them was taken at all (else the
-// reference's table still holds 0). Streams are padded to a multiple of 4 (one wave).
-inline size_t viterbi_work_bytes(size_t nstreams, size_t n_syms) { return (nstreams + 3) / 4 * 4 * n_syms * 4; }
+// ---- the batched decode's scratch (k_psk31.hip): the survivor words of K = 5, trellis.hpp ----
+inline size_t viterbi_work_bytes(size_t nstreams, size_t n_syms) { return trellis::work_bytes(4, nstreams, n_syms); }
 
 }  // namespace psk31
 }  // namespace orion

@@ -1,5 +1,6 @@
 // psk31_blocks.hpp — PSK31 on the device over k_psk31.hip (host side): the batched Viterbi
-// decode and the demodulator bank. The scalar code they are held to is psk31.hpp.
+// decode (the wave engine of trellis_wave.hpp) and the demodulator bank. The scalar code they
+// are held to is psk31.hpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -33,7 +33,9 @@ host's for every input, ties and non-finite values included.
 Shapes: 1, 4, 5 and 9 streams put one, four, and four-plus-one streams into a wave and use
 one to three workgroups, with the last wave partly empty; 1, 2 and 5 symbols end before
 every state is reachable and inside the first group of eight symbols the kernel fetches
-ahead, 33 and 300 cross that group with and without a remainder."""
+ahead, 33 and 300 cross that group with and without a remainder; 7, 8, 9, 15, 16 and 17 sit
+on either side of the first two edges of that group, which the step loop and the traceback
+(eight survivor words ahead) both have."""
 import functools
 
 import numpy as np
@@ -45,6 +47,7 @@ from conftest import report
 pytestmark = pytest.mark.gpu
 
 STREAMS = (1, 4, 5, 9)
+GROUP_EDGE_LENGTHS = (7, 8, 9, 15, 16, 17)
 
 # ---- the demodulator bank ---------------------------------------------------------------
 FS = 8000.0
@@ -275,6 +278,16 @@ def test_viterbi_batch_equals_the_host_decoder(gpu_lib, n_syms, kind):
         assert got.tobytes() == _host(gpu_lib, soft).tobytes(), (nstreams, n_syms, kind)
     # the restatement's own bits for the first stream (cached by the CPU tests' cases)
     assert got[0].tobytes() == P.viterbi_case(n_syms, kind, 0)[1].tobytes()
+
+
+@pytest.mark.parametrize("kind", P.VITERBI_KINDS)
+@pytest.mark.parametrize("n_syms", GROUP_EDGE_LENGTHS)
+def test_viterbi_batch_equals_the_host_decoder_at_the_group_edges(gpu_lib, n_syms, kind):
+    for nstreams in STREAMS:
+        soft = _batch(nstreams, n_syms, kind)
+        got = gpu_lib.psk31_viterbi_batch(soft)
+        assert got.dtype == np.uint8 and got.shape == (nstreams, n_syms)
+        assert got.tobytes() == _host(gpu_lib, soft).tobytes(), (nstreams, n_syms, kind)
 
 
 def test_viterbi_batch_is_independent_of_its_neighbours(gpu_lib):
