@@ -1356,6 +1356,99 @@ int orion_frame_bytes_to_bits_batch(const uint8_t* in, size_t nframes, size_t nb
 int orion_frame_bytes_to_bits_batch_device(const uint8_t* in, size_t nframes, size_t nbytes, uint8_t* out,
                                            void* stream);
 
+/* ---- OFDM burst acquisition: Schmidl & Cox packet search, fractional and integer carrier
+ * offset (sync/ofdm_sync.rs:354-589). The host entries are the reference in its f32 operation
+ * order; the batched search runs one independent search per capture on the GPU. ---- */
+/* OfdmPreamble (sync/ofdm_sync.rs:45-75): training != 0 adds a training symbol of
+ * training_n_fft + training_cp_len samples after the repeats. */
+typedef struct {
+  size_t num_repeats, repeat_len;
+  int32_t training;
+  size_t training_n_fft, training_cp_len;
+} orion_ofdm_preamble;
+/* OfdmSyncResult (sync/ofdm_sync.rs:94-107). */
+typedef struct {
+  int64_t start_sample;
+  float cfo_hz;
+  int32_t integer_cfo_bins;
+  float score;
+  uint32_t reserved;
+} orion_ofdm_sync_result;
+#define ORION_OFDM_SYNC_TOP 5 /* the integer search runs for this many ranked results */
+/* The number of candidate offsets of a search, end - search_start with end = min(search_end,
+ * n - total_len); 0 where ofdm_sync returns nothing whatever the samples. */
+size_t orion_ofdm_sync_offsets(size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                               size_t search_end);
+/* ofdm_sync on the host: iq [n] cf32 -> results [cap] ranked, *count of them (cap >=
+ * orion_ofdm_sync_offsets(..)); r_peak (may be NULL) the largest window energy of a kept offset. */
+int orion_ofdm_sync_host(const void* iq, size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                         size_t search_end, orion_ofdm_sync_result* results, size_t cap, size_t* count, float* r_peak);
+/* The sums ofdm_sync ranks, per offset of the same range: p [offsets] cf32, r [offsets] f32. */
+int orion_ofdm_sc_metric_host(const void* iq, size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                              size_t search_end, void* p, float* r);
+/* earliest_accepted (sync/ofdm_sync.rs:488-503): *index into results, or -1. */
+int orion_ofdm_earliest_accepted(const orion_ofdm_sync_result* results, size_t n, float score_threshold,
+                                 size_t cluster_len, int64_t* index);
+/* estimate_integer_cfo_bins (sync/ofdm_sync.rs:513-562) of the training symbol at
+ * training_start; corr2 (may be NULL) [training_n_fft + 1] receives |corr|^2 per shift from
+ * -training_n_fft / 2 on. */
+int orion_ofdm_integer_cfo_host(const void* iq, size_t n, float fs, size_t training_n_fft, size_t training_cp_len,
+                                size_t training_start, float fractional_cfo_hz, int32_t* bins, float* corr2);
+/* Rotator::new(freq_hz, fs).rotate_block (dsp/rotator.rs:74-84) from a fresh oscillator: in,
+ * out [n] cf32. */
+int orion_ofdm_rotate_block_host(float freq_hz, float fs, const void* in, size_t n, void* out);
+/* remove_common_phase_error (demodulate/ofdm_frame.rs:200-274) in place over syms
+ * [n_sym][n_data] cf32 of a constellation (ORION_OFDM_*); nothing below 4 symbols. */
+int orion_ofdm_cpe_host(int constellation, void* syms, size_t n_sym, size_t n_data);
+/* The equalizer branch of soft_demap (demodulate/ofdm_frame.rs:95-134) on the host: n_sym
+ * symbols of iq at the configuration's plan and RX window back-off, equalized by the weights
+ * of training_freq [n_fft] cf32 (the received training symbol's transform at the same window),
+ * the phase tracker, then the LLRs of constellation. syms [n_sym * n_data] cf32, llr [n_sym *
+ * n_data * bits] f32 (may be NULL). No gain is divided out. */
+int orion_ofdm_soft_demap_equalized_host(const orion_ofdm_config* cfg, int constellation, const void* iq, size_t n_sym,
+                                         const void* training_freq, void* syms, float* llr);
+/* What the batched search writes, device pointers: per offset p [ncap][offsets] cf32, r, score
+ * (-1 at an offset ofdm_sync skips), cfo_hz [ncap][offsets] f32; per capture r_peak [ncap],
+ * top_start / top_bins [ncap][5] i32 (the first five of ofdm_sync's ranking; -1 / 0 padded),
+ * accepted_start [ncap] (earliest_accepted's choice at the call's threshold with cluster_len =
+ * the preamble's total length; -1: none), accepted_in_top [ncap] (which of the five it is, or
+ * -1), accepted_bins (its top-five entry, or 0), accepted_score, accepted_cfo_hz. */
+typedef struct {
+  void* p;
+  float *r, *score, *cfo_hz, *r_peak;
+  int32_t *top_start, *top_bins, *accepted_start, *accepted_in_top, *accepted_bins;
+  float *accepted_score, *accepted_cfo_hz;
+} orion_ofdm_sync_out;
+/* NULL (and a message) for a training symbol the transform does not take. No device is touched. */
+typedef struct orion_ofdm_acquire orion_ofdm_acquire;
+orion_ofdm_acquire* orion_ofdm_acquire_new(const orion_ofdm_preamble* pre);
+void orion_ofdm_acquire_free(orion_ofdm_acquire* a);
+/* iq [ncap][n] cf32 on the device, finite; the range must hold an offset
+ * (orion_ofdm_sync_offsets > 0). Asynchronous on stream. */
+int orion_ofdm_sync_batch_device(orion_ofdm_acquire* a, const void* iq, size_t ncap, size_t n, float fs,
+                                 size_t search_start, size_t search_end, float score_threshold,
+                                 const orion_ofdm_sync_out* out, void* stream);
+/* rows [ncap][n] cf32: capture c from sync->accepted_start[c] on, times the closed-form phasor
+ * of -(accepted_cfo_hz + accepted_bins fs / n_fft) with the Rotator's phase index (k + 1 at
+ * sample k), zero past the capture's end and in a capture with no accepted candidate; avail
+ * [ncap] i32 the samples a row holds (0: none), total_cfo [ncap] f32. Only the three accepted_*
+ * arrays named here are read. Asynchronous on stream. */
+int orion_ofdm_acquire_correct_device(orion_ofdm_acquire* a, const void* iq, size_t ncap, size_t n, float fs, size_t n_fft,
+                                      const orion_ofdm_sync_out* sync, void* rows, int32_t* avail, float* total_cfo,
+                                      void* stream);
+/* weights [ncap][training_n_fft] cf32: the corrected rows' training symbol transformed window
+ * samples into the symbol (cp_len - RX window back-off), divided by the known pattern, then
+ * equalizer_weight (demodulate/ofdm.rs:440-502). The preamble must carry a training symbol. */
+int orion_ofdm_acquire_weights_device(orion_ofdm_acquire* a, const void* rows, size_t ncap, size_t n, size_t window,
+                                      void* weights, void* stream);
+/* The equalizer branch of the frame demodulator's soft_demap on the device, for frames of
+ * n_symbols symbols of a demodulator handle's constellation: raw [frames][n_symbols * n_data]
+ * cf32 (orion_ofdm_demod_device with no equalizer and gain 1) times weights [frames][n_fft] at
+ * the data bins, remove_common_phase_error per frame (one wave each) -> syms, then their LLRs
+ * -> llr [frames][n_symbols * n_data * bits] (may be NULL). */
+int orion_ofdm_equalize_track_device(orion_ofdm* h, const void* raw, const void* weights, size_t frames, size_t n_symbols,
+                                     void* syms, float* llr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

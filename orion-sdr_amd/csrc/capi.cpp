@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "acquire.hpp"
 #include "bch.hpp"
 #include "bch_blocks.hpp"
 #include "blocks.hpp"
@@ -78,6 +79,13 @@ struct orion_fft {
   orion::FftDev impl;
   orion_fft(size_t n, bool inverse) : impl(n, inverse) {}
 };
+struct orion_ofdm_acquire {
+  orion::AcquireEngine impl;
+  explicit orion_ofdm_acquire(const orion::acquire::Preamble& p) : impl(p) {}
+};
+static_assert(sizeof(orion_ofdm_sync_result) == sizeof(orion::acquire::SyncResult) && sizeof(orion_ofdm_sync_result) == 24 &&
+                  sizeof(orion_ofdm_sync_out) == sizeof(orion::SyncOut) && ORION_OFDM_SYNC_TOP == orion::acquire::kTopN,
+              "orion_ofdm_sync_result / orion_ofdm_sync_out are acquire.hpp's records");
 enum { kOfdmMod = 0, kOfdmDemod = 1, kOfdmDecider = 2, kOfdmSoftDemod = 3, kOfdmEqualizer = 4 };
 struct orion_ofdm {
   int kind;
@@ -2657,6 +2665,151 @@ int orion_frame_bytes_to_bits_batch_device(const uint8_t* in, size_t nframes, si
   if (nframes && nbytes && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
   return guarded([&] {
     orion::frame_bytes_to_bits_batch(in, nframes, nbytes, out, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+
+// ---- OFDM burst acquisition (acquire.hpp) ----
+static orion::acquire::Preamble preamble_of(const orion_ofdm_preamble* p) {
+  orion::acquire::Preamble q;
+  q.num_repeats = p->num_repeats;
+  q.repeat_len = p->repeat_len;
+  q.training = p->training != 0;
+  q.tn_fft = q.training ? p->training_n_fft : 0;
+  q.tcp = q.training ? p->training_cp_len : 0;
+  return q;
+}
+size_t orion_ofdm_sync_offsets(size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                               size_t search_end) {
+  if (!pre) return 0;
+  const orion::acquire::Preamble q = preamble_of(pre);
+  if (!orion::acquire::search_ok(n, fs, q, search_start, search_end)) return 0;
+  return orion::acquire::search_end(n, q, search_end) - search_start;
+}
+int orion_ofdm_sync_host(const void* iq, size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                         size_t search_end, orion_ofdm_sync_result* results, size_t cap, size_t* count, float* r_peak) {
+  if (!pre || !count || (n && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const std::vector<orion::acquire::SyncResult> r =
+        orion::acquire::ofdm_sync(static_cast<const float*>(iq), n, fs, preamble_of(pre), search_start, search_end, r_peak);
+    if (r.size() > cap || (r.size() && !results)) return fail(ORION_E_ARG, "ofdm_sync: results holds fewer than the offsets");
+    if (!r.empty()) std::memcpy(results, r.data(), r.size() * sizeof(orion_ofdm_sync_result));
+    *count = r.size();
+    return ORION_OK;
+  });
+}
+int orion_ofdm_sc_metric_host(const void* iq, size_t n, float fs, const orion_ofdm_preamble* pre, size_t search_start,
+                              size_t search_end, void* p, float* r) {
+  if (!pre || (n && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::acquire::Preamble q = preamble_of(pre);
+    if (!orion::acquire::search_ok(n, fs, q, search_start, search_end)) return ORION_OK;
+    if (!p || !r) return fail(ORION_E_NULL, "null buffer");
+    orion::acquire::sc_metric(static_cast<const float*>(iq), q, search_start, orion::acquire::search_end(n, q, search_end),
+                              static_cast<float*>(p), r);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_earliest_accepted(const orion_ofdm_sync_result* results, size_t n, float score_threshold,
+                                 size_t cluster_len, int64_t* index) {
+  if (!index || (n && !results)) return fail(ORION_E_NULL, "null buffer");
+  *index = orion::acquire::earliest_accepted(reinterpret_cast<const orion::acquire::SyncResult*>(results), n,
+                                             score_threshold, cluster_len);
+  return ORION_OK;
+}
+int orion_ofdm_integer_cfo_host(const void* iq, size_t n, float fs, size_t training_n_fft, size_t training_cp_len,
+                                size_t training_start, float fractional_cfo_hz, int32_t* bins, float* corr2) {
+  if (!bins || (n && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    *bins = orion::acquire::estimate_integer_cfo_bins(static_cast<const float*>(iq), n, fs, training_n_fft, training_cp_len,
+                                                      training_start, fractional_cfo_hz, corr2);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_rotate_block_host(float freq_hz, float fs, const void* in, size_t n, void* out) {
+  if (n && (!in || !out)) return fail(ORION_E_NULL, "null buffer");
+  orion::acquire::rotate_block(freq_hz, fs, static_cast<const float*>(in), n, static_cast<float*>(out));
+  return ORION_OK;
+}
+int orion_ofdm_cpe_host(int constellation, void* syms, size_t n_sym, size_t n_data) {
+  if (n_sym && n_data && !syms) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    if (orion::ofdm::bits_per_symbol(constellation) == 0) return fail(ORION_E_ARG, "unknown constellation");
+    orion::acquire::remove_common_phase_error(constellation, static_cast<float*>(syms), n_sym, n_data);
+    return ORION_OK;
+  });
+}
+int orion_ofdm_soft_demap_equalized_host(const orion_ofdm_config* cfg, int constellation, const void* iq, size_t n_sym,
+                                         const void* training_freq, void* syms, float* llr) {
+  if (!cfg) return fail(ORION_E_NULL, "null configuration");
+  if (!training_freq || (n_sym && (!iq || !syms))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    if (orion::ofdm::bits_per_symbol(constellation) == 0) return fail(ORION_E_ARG, "unknown constellation");
+    orion::ofdm::Config c = cfg->impl;
+    c.constellation = constellation;
+    orion::acquire::soft_demap_equalized(c, static_cast<const float*>(iq), n_sym, static_cast<const float*>(training_freq),
+                                         static_cast<float*>(syms), llr);
+    return ORION_OK;
+  });
+}
+orion_ofdm_acquire* orion_ofdm_acquire_new(const orion_ofdm_preamble* pre) {
+  if (!pre) {
+    fail(ORION_E_NULL, "null preamble");
+    return nullptr;
+  }
+  try {
+    return new orion_ofdm_acquire(preamble_of(pre));
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void orion_ofdm_acquire_free(orion_ofdm_acquire* a) { delete a; }
+int orion_ofdm_sync_batch_device(orion_ofdm_acquire* a, const void* iq, size_t ncap, size_t n, float fs,
+                                 size_t search_start, size_t search_end, float score_threshold,
+                                 const orion_ofdm_sync_out* out, void* stream) {
+  if (!a) return fail(ORION_E_NULL, "null handle");
+  if (!out || (ncap && !iq)) return fail(ORION_E_NULL, "null buffer");
+  const void* const* f = reinterpret_cast<const void* const*>(out);
+  for (size_t k = 0; k < sizeof(orion_ofdm_sync_out) / sizeof(void*); ++k)
+    if (ncap && !f[k]) return fail(ORION_E_NULL, "null output");
+  return guarded([&] {
+    orion::SyncOut o;
+    std::memcpy(&o, out, sizeof(o));
+    a->impl.sync_batch(iq, ncap, n, fs, search_start, search_end, score_threshold, o, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_acquire_correct_device(orion_ofdm_acquire* a, const void* iq, size_t ncap, size_t n, float fs, size_t n_fft,
+                                      const orion_ofdm_sync_out* sync, void* rows, int32_t* avail, float* total_cfo,
+                                      void* stream) {
+  if (!a) return fail(ORION_E_NULL, "null handle");
+  if (!sync || (ncap && n && (!iq || !rows || !avail || !total_cfo || !sync->accepted_start || !sync->accepted_cfo_hz ||
+                              !sync->accepted_bins)))
+    return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::SyncOut o;
+    std::memcpy(&o, sync, sizeof(o));
+    a->impl.correct(iq, ncap, n, fs, n_fft, o, rows, avail, total_cfo, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_acquire_weights_device(orion_ofdm_acquire* a, const void* rows, size_t ncap, size_t n, size_t window,
+                                      void* weights, void* stream) {
+  if (!a) return fail(ORION_E_NULL, "null handle");
+  if (ncap && (!rows || !weights)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    a->impl.weights(rows, ncap, n, window, weights, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_ofdm_equalize_track_device(orion_ofdm* h, const void* raw, const void* weights, size_t frames, size_t n_symbols,
+                                     void* syms, float* llr, void* stream) {
+  if (!h) return fail(ORION_E_NULL, "null handle");
+  if (h->kind != kOfdmDemod) return fail(ORION_E_TYPE, "not a demodulator");
+  if (frames && n_symbols && (!raw || !weights || !syms)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    h->impl.equalize_track(raw, weights, frames, n_symbols, syms, llr, static_cast<hipStream_t>(stream));
     return ORION_OK;
   });
 }

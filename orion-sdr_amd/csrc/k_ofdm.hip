@@ -23,6 +23,7 @@
 // fallback path.
 #include "hip_common.hpp"
 #include "ofdm_blocks.hpp"
+#include "ofdm_dev.hpp"
 
 namespace orion {
 
@@ -75,77 +76,6 @@ __device__ __forceinline__ void fft_lds(f2* x, int n, int log2n, const f2* __res
   __syncthreads();
 }
 
-// ---- constellations (ofdm.cpp map_bits / decide / soft_llr) ---------------------------
-__device__ __forceinline__ f2 map_point(int order, const uint8_t* __restrict__ b, const float* __restrict__ axis) {
-  const float r = 0.70710678118654752440f;
-  if (order == ofdm::kBpsk) return f2{(b[0] & 1u) == 0 ? 1.0f : -1.0f, 0.0f};
-  if (order == ofdm::kQpsk) return f2{(b[0] & 1u) == 0 ? r : -r, (b[1] & 1u) == 0 ? r : -r};
-  const int k = order;  // kQam16 = 2, kQam64 = 3, kQam256 = 4: the bits per axis
-  int ii = 0, iq = 0;
-  for (int i = 0; i < k; ++i) {
-    ii = (ii << 1) | (b[i] & 1);
-    iq = (iq << 1) | (b[k + i] & 1);
-  }
-  return f2{axis[ii], axis[iq]};
-}
-__device__ __forceinline__ int decide_axis(float v, int k, const float* __restrict__ thr) {
-  int nat = 0;
-  for (int t = 0; t < (1 << k) - 1; ++t) nat += v > thr[t] ? 1 : 0;
-  return nat ^ (nat >> 1);
-}
-__device__ __forceinline__ void decide_sym(int order, f2 v, const float* __restrict__ thr, uint8_t* __restrict__ out) {
-  if (order == ofdm::kBpsk) {
-    out[0] = v.x < 0.0f ? 1 : 0;
-  } else if (order == ofdm::kQpsk) {
-    out[0] = v.x < 0.0f ? 1 : 0;
-    out[1] = v.y < 0.0f ? 1 : 0;
-  } else {
-    const int k = order;
-    const int gi = decide_axis(v.x, k, thr), gq = decide_axis(v.y, k, thr);
-    for (int b = 0; b < k; ++b) {
-      out[b] = static_cast<uint8_t>((gi >> (k - 1 - b)) & 1);
-      out[k + b] = static_cast<uint8_t>((gq >> (k - 1 - b)) & 1);
-    }
-  }
-}
-__device__ __forceinline__ void axis_llr(float v, int k, const float* __restrict__ axis, float* __restrict__ out) {
-  for (int b = 0; b < k; ++b) {
-    const int shift = k - 1 - b;
-    float d0 = __builtin_inff(), d1 = __builtin_inff();
-    for (int g = 0; g < (1 << k); ++g) {
-      const float d = (v - axis[g]) * (v - axis[g]);
-      if (((g >> shift) & 1) == 0)
-        d0 = fminf(d0, d);
-      else
-        d1 = fminf(d1, d);
-    }
-    out[b] = d1 - d0;
-  }
-}
-__device__ __forceinline__ void llr_sym(int order, f2 v, const float* __restrict__ axis, float* __restrict__ out) {
-  if (order == ofdm::kBpsk) {
-    out[0] = 4.0f * v.x;
-  } else if (order == ofdm::kQpsk) {
-    const float scale = 4.0f * 1.41421356237309504880f;
-    out[0] = scale * v.x;
-    out[1] = scale * v.y;
-  } else {
-    const int k = order;
-    axis_llr(v.x, k, axis, out);
-    axis_llr(v.y, k, axis, out + k);
-  }
-}
-
-// ---- the equalizer (ofdm.cpp cdiv / equalizer_weight / interpolate_at) ----------------
-__device__ __forceinline__ f2 cdiv_nc(f2 a, f2 b) {
-  const float ns = b.x * b.x + b.y * b.y;
-  return f2{(a.x * b.x + a.y * b.y) / ns, (a.y * b.x - a.x * b.y) / ns};
-}
-__device__ __forceinline__ f2 cmul_nc(f2 a, f2 b) { return f2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ f2 eq_weight(f2 h) {
-  const float m = h.x * h.x + h.y * h.y;
-  return m >= ofdm::kEqualizerFloor ? f2{h.x / m, -h.y / m} : f2{0.0f, 0.0f};
-}
 // The estimate at bin from np > 0 bin-sorted pilots; rx(bin) is the received value of a bin.
 // The two bracketing pilots' ratios are computed here, per bin, by binary search as the
 // reference does; no ratio table is kept between bins.

@@ -125,6 +125,22 @@ const OfdmDev& OfdmEngine::dev(hipStream_t s) {
   return d_;
 }
 
+void OfdmEngine::equalize_track(const void* raw, const void* weights, size_t frames, size_t nsym, void* syms, float* llr,
+                                hipStream_t s) {
+  if (frames == 0 || nsym == 0) return;
+  if (frames > kMaxSymbols || nsym > (size_t{1} << 20) || frames * nsym > kMaxSymbols)
+    throw std::invalid_argument("ofdm: more than 2^30 symbols in one call");
+  if (nsym * num_data() >= (size_t{1} << 31)) throw std::invalid_argument("ofdm: a frame of 2^31 soft symbols or more");
+  check_ptr8(raw);
+  check_ptr8(weights);
+  check_ptr8(syms);
+  const OfdmDev& d = dev(s);
+  launch_frame_eq_cpe(static_cast<const f2*>(raw), static_cast<const f2*>(weights), static_cast<long long>(frames),
+                      static_cast<int>(nsym), d, static_cast<f2*>(syms), s);
+  if (llr)
+    launch_ofdm_llr(static_cast<const f2*>(syms), static_cast<long long>(frames * nsym * d.nd), d.order, d.axis, llr, s);
+}
+
 void OfdmEngine::estimate_channel(const float* received, size_t n) {
   if (!eq_) throw std::invalid_argument("ofdm: this handle has no equalizer");
   eq_->estimate_from_training_symbol(received, n);

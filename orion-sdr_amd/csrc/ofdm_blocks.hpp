@@ -49,6 +49,10 @@ void launch_ofdm_demod(const f2* iq, f2* soft, uint8_t* bits, float* llr, long l
 void launch_ofdm_decide(const f2* soft, long long n, int order, const float* thr, uint8_t* bits, hipStream_t s);
 void launch_ofdm_llr(const f2* soft, long long n, int order, const float* axis, float* llr, hipStream_t s);
 void launch_ofdm_equalize(const f2* in, f2* out, long long nsym, const OfdmDev& c, int eq, hipStream_t s);
+// k_acquire.hip: raw [frames][nsym][nd] soft symbols (no equalizer, no gain) times each frame's
+// weights [frames][n] at the data bins, then remove_common_phase_error per frame -> out.
+void launch_frame_eq_cpe(const f2* raw, const f2* weights, long long frames, int nsym, const OfdmDev& c, f2* out,
+                         hipStream_t s);
 
 // FftBlock / IfftBlock (multicarrier/fft.rs) on the device. Constructing one touches no
 // device; the twiddles are uploaded by the first call.
@@ -93,6 +97,12 @@ class OfdmEngine {
   void soft_demod(const void* soft, size_t n, float* llr, hipStream_t s);
   // OfdmEqualizer::process over nsym n_fft-bin vectors (not in place).
   void equalize(const void* in, size_t nsym, void* out, hipStream_t s);
+  // The equalizer branch of the frame demodulator's soft_demap for frames of nsym symbols each:
+  // raw [frames][nsym * nd] (this engine's demodulate with no equalizer and no gain) and
+  // weights [frames][n_fft] -> syms [frames][nsym * nd] after the phase tracker, and llr
+  // [frames][nsym * nd * bps] (may be null) from them.
+  void equalize_track(const void* raw, const void* weights, size_t frames, size_t nsym, void* syms, float* llr,
+                      hipStream_t s);
   // estimate_from_training_symbol: received [n_fft] cf32 in host memory.
   void estimate_channel(const float* received, size_t n);
   // set_pilot_bins: the equalizer stage's tables are rebuilt by the next call.

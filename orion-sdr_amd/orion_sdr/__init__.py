@@ -3089,6 +3089,27 @@ class OfdmDemod(_OfdmHandle):
         self.process_host_into(iq, out)
         return out
 
+    def equalize_track(self, raw, weights, n_symbols, llr=True, stream=None):
+        """The equalizer branch of the frame demodulator's soft_demap on the GPU, for frames of
+        n_symbols symbols: raw (frames, n_symbols * data carriers) soft symbols of a
+        demodulator with no equalizer and gain 1, weights (frames, n_fft) per-frame equalizer
+        coefficients -> (symbols after the common-phase-error tracker, their LLRs or None).
+        Contiguous complex64 CUDA tensors, queued on torch's current stream or on stream."""
+        import torch
+
+        for t, w in ((raw, n_symbols * self.num_data_carriers), (weights, self.n_fft)):
+            if not _is_torch(t) or not t.is_cuda or not t.is_contiguous() or t.dtype != torch.complex64 or t.dim() != 2 \
+                    or int(t.shape[1]) != w or int(t.shape[0]) != int(raw.shape[0]):
+                raise ValueError("equalize_track: contiguous complex64 CUDA tensors (frames, n_symbols * data carriers) "
+                                 "and (frames, n_fft)")
+        syms = torch.empty_like(raw)
+        out = torch.empty((raw.shape[0], n_symbols * self.bits_per_ofdm_symbol), dtype=torch.float32, device=raw.device) \
+            if llr else None
+        _arg_check(_L.orion_ofdm_equalize_track_device(self._h, raw.data_ptr(), weights.data_ptr(), int(raw.shape[0]),
+                                                       int(n_symbols), syms.data_ptr(), out.data_ptr() if llr else None,
+                                                       SyncEngine._stream(raw, stream)))
+        return syms, out
+
 
 def ofdm_modulate_batch(mod: OfdmMod, bits, stream=None):
     """n_channels x n_symbols symbols in one launch: uint8 (n_channels, n_symbols *
@@ -5261,25 +5282,48 @@ class OfdmFrameDemod(_FrameLayer):
             return self.decode_frames(torch.from_numpy(np.ascontiguousarray(iq)).cuda(), stream)
         if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
             raise ValueError("iq: expected a contiguous 2-D complex64 CUDA tensor")
+        def llr_of(constellation, block, idx):
+            return ofdm_demodulate_batch(self.demod(constellation), block, bits=False, llr=True, stream=stream)[2]
+
+        res, incomplete = self._decode_rows(iq, stream, llr_of)
+        res["error"][incomplete] = RX_ERRORS["malformed_header"]  # truncated input, as decode reports it
+        return res
+
+    def _decode_rows(self, iq, stream, llr_of, avail=None):
+        """What decode_frames and OfdmBurstDemod.receive_frames share: rows (nframes, n) on the
+        device, each from the first sample after the preamble and training symbol. The headers
+        are decoded on the device, the parsed fields come to the host in one small copy, the
+        frames are grouped by (mcs_index, payload_len) and each group's payload chain is launched.
+        llr_of(constellation, block, idx) gives the LLRs of block (k, whole symbols), rows idx of
+        iq (None: every row). avail (int tensor, nframes): the samples a row really holds (default
+        n). Returns (the result dict, incomplete): incomplete marks rows with too few samples for
+        the header or for the payload their header declares; nothing else is set for them."""
+        import torch
+
         ns, n = int(iq.shape[0]), int(iq.shape[1])
         res = {k: np.zeros(ns, np.int64) for k in ("error", "mcs_index", "sequence_num", "flags", "payload_len")}
         res.update({k: np.zeros(ns, bool) for k in ("inner_ok", "outer_ok", "crc_ok")})
         res["payloads"] = [np.zeros(0, np.uint8) for _ in range(ns)]
+        incomplete = np.zeros(ns, bool)
         hl = self.header_symbols * self.sps
         if n < hl or ns == 0:
-            res["error"][:] = RX_ERRORS["malformed_header"]
-            return res
+            incomplete[:] = True
+            return res, incomplete
         with _TorchOn(iq, stream):
-            hllr = ofdm_demodulate_batch(self.demod(HEADER_CONSTELLATION), iq[:, :hl].contiguous(), bits=False, llr=True,
-                                         stream=stream)[2]
+            hllr = llr_of(HEADER_CONSTELLATION, iq[:, :hl].contiguous(), None)
             h = frame_decode_chain_batch(hllr, HEADER_FIELD_BYTES, self.header_scheme, ldpc_rule="sum_product",
                                          header=True, stream=stream)
             if stream is not None:
                 torch.cuda.current_stream(iq.device).synchronize()
-            head = torch.cat([h["fields"], h["valid"].to(torch.int64)[:, None]], dim=1).cpu().numpy()  # the one copy
+            cols = [h["fields"], h["valid"].to(torch.int64)[:, None]]
+            if avail is not None:
+                cols.append(avail.to(torch.int64)[:, None])
+            head = torch.cat(cols, dim=1).cpu().numpy()  # the one copy
+            have = head[:, 6] if avail is not None else np.full(ns, n, np.int64)
             E = RX_ERRORS
-            valid = head[:, 5] != 0
-            res["error"][~valid] = E["header_crc_mismatch"]
+            incomplete |= have < hl
+            valid = (head[:, 5] != 0) & ~incomplete
+            res["error"][~valid & ~incomplete] = E["header_crc_mismatch"]
             for col, key in ((0, "mcs_index"), (1, "payload_len"), (2, "sequence_num"), (3, "flags")):
                 res[key][valid] = head[valid, col]
             known = valid & (head[:, 0] < len(self.mcs_table)) & (head[:, 1] <= (1 << 16))  # the device chain's block limit
@@ -5290,12 +5334,14 @@ class OfdmFrameDemod(_FrameLayer):
                 mcs = self.mcs_table.get(mcs_index)
                 sch = self.scheme(mcs)
                 plen_sym = self.payload_symbols(mcs, block_plan(plen, sch)) * self.sps
-                if n - hl < plen_sym:
-                    res["error"][rows] = RX_ERRORS["malformed_header"]
+                short = (have[rows] - hl < plen_sym) | (n - hl < plen_sym)
+                incomplete[rows[short]] = True
+                rows = rows[~short]
+                if rows.size == 0:
                     continue
                 idx = torch.from_numpy(rows).to(iq.device)
                 body = iq.index_select(0, idx)[:, hl:hl + plen_sym].contiguous()
-                llr = ofdm_demodulate_batch(self.demod(mcs.constellation), body, bits=False, llr=True, stream=stream)[2]
+                llr = llr_of(mcs.constellation, body, idx)
                 seeds = h["fields"].index_select(0, idx)[:, 4].contiguous() if sch.per_frame_seed else None
                 out = frame_decode_chain_batch(llr, plen, sch, seeds=seeds, ldpc_rule=self.f["ldpc_decode_rule"], stream=stream)
                 if stream is not None:
@@ -5306,4 +5352,492 @@ class OfdmFrameDemod(_FrameLayer):
                 res["error"][rows[~flg[:, 3]]] = E["crc_mismatch"]
                 for j in np.flatnonzero(flg[:, 3]):
                     res["payloads"][rows[j]] = pay[j]
-        return res
+        return res, incomplete
+
+
+# ---- OFDM burst acquisition: the Schmidl & Cox packet search, fractional and integer carrier
+# offset (src/sync/ofdm_sync.rs:354-589) ----
+class _PreambleC(C.Structure):
+    _fields_ = [("num_repeats", C.c_size_t), ("repeat_len", C.c_size_t), ("training", C.c_int32),
+                ("training_n_fft", C.c_size_t), ("training_cp_len", C.c_size_t)]
+
+
+class _SyncOutC(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("p", "r", "score", "cfo_hz", "r_peak", "top_start", "top_bins", "accepted_start",
+                                          "accepted_in_top", "accepted_bins", "accepted_score", "accepted_cfo_hz")]
+
+
+_SYNC_RESULT = np.dtype([("start_sample", np.int64), ("cfo_hz", np.float32), ("integer_cfo_bins", np.int32),
+                         ("score", np.float32), ("reserved", np.uint32)])
+OFDM_SYNC_TOP = 5
+
+
+def _acquire_sigs():
+    vp, sz, f, i, pp = C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.POINTER(_PreambleC)
+    sig = {
+        "orion_ofdm_sync_offsets": (sz, [sz, f, pp, sz, sz]),
+        "orion_ofdm_sync_host": (i, [vp, sz, f, pp, sz, sz, vp, sz, C.POINTER(sz), C.POINTER(f)]),
+        "orion_ofdm_sc_metric_host": (i, [vp, sz, f, pp, sz, sz, vp, vp]),
+        "orion_ofdm_earliest_accepted": (i, [vp, sz, f, sz, C.POINTER(C.c_int64)]),
+        "orion_ofdm_integer_cfo_host": (i, [vp, sz, f, sz, sz, sz, f, C.POINTER(C.c_int32), vp]),
+        "orion_ofdm_acquire_new": (vp, [pp]), "orion_ofdm_acquire_free": (None, [vp]),
+        "orion_ofdm_sync_batch_device": (i, [vp, vp, sz, sz, f, sz, sz, f, C.POINTER(_SyncOutC), vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_acquire_sigs()
+__all__ += ["OfdmSyncResult", "OFDM_SYNC_TOP", "ofdm_sync", "ofdm_sc_metric", "earliest_accepted", "ofdm_integer_cfo",
+            "ofdm_sync_batch"]
+
+
+class OfdmSyncResult:
+    """OfdmSyncResult (sync/ofdm_sync.rs:94-107): the preamble's start, the fractional carrier
+    offset in Hz (float32), the integer one in subcarrier spacings and the raw timing score."""
+
+    def __init__(self, start_sample, cfo_hz, integer_cfo_bins, score):
+        self.start_sample, self.cfo_hz = int(start_sample), np.float32(cfo_hz)
+        self.integer_cfo_bins, self.score = int(integer_cfo_bins), np.float32(score)
+
+    def __repr__(self):
+        return (f"OfdmSyncResult(start_sample={self.start_sample}, cfo_hz={self.cfo_hz}, "
+                f"integer_cfo_bins={self.integer_cfo_bins}, score={self.score})")
+
+
+def _preamble_c(preamble) -> _PreambleC:
+    if not isinstance(preamble, OfdmPreamble):
+        raise ValueError("preamble: an OfdmPreamble")
+    tr = preamble.training
+    return _PreambleC(preamble.num_repeats, preamble.repeat_len, 1 if tr else 0, tr[0] if tr else 0, tr[1] if tr else 0)
+
+
+def _search_range(search_start, search_end):
+    a, b = int(search_start), int(search_end)
+    if a < 0 or b < 0:
+        raise ValueError("a search range is not negative")
+    return a, min(b, (1 << 63) - 1)
+
+
+def ofdm_sync(iq, fs, preamble, search_start, search_end) -> list:
+    """ofdm_sync (sync/ofdm_sync.rs:361-463) on the host: every offset of iq[search_start:
+    min(search_end, len - preamble.total_len)] whose window holds energy, ranked by score (r /
+    r_peak) (stable, descending) with the raw score reported; the integer search runs for the
+    first five when the preamble has a training symbol. Empty for repeat_len == 0, num_repeats
+    < 2, fs <= 0 or a range that holds no offset."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    pc = _preamble_c(preamble)
+    a, b = _search_range(search_start, search_end)
+    cap = int(_L.orion_ofdm_sync_offsets(iq.size, float(fs), C.byref(pc), a, b))
+    res, count = np.zeros(max(cap, 1), _SYNC_RESULT), C.c_size_t(0)
+    _arg_check(_L.orion_ofdm_sync_host(iq.ctypes.data, iq.size, float(fs), C.byref(pc), a, b, res.ctypes.data, cap,
+                                       C.byref(count), None))
+    return [OfdmSyncResult(r["start_sample"], r["cfo_hz"], r["integer_cfo_bins"], r["score"]) for r in res[:count.value]]
+
+
+def ofdm_sc_metric(iq, fs, preamble, search_start, search_end):
+    """(p complex64, r float32) per offset of ofdm_sync's range, the sums it ranks: P(d) summed
+    over the adjacent segment pairs and the energy R(d) of the later segments; host only."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    pc = _preamble_c(preamble)
+    a, b = _search_range(search_start, search_end)
+    nd = int(_L.orion_ofdm_sync_offsets(iq.size, float(fs), C.byref(pc), a, b))
+    p, r = np.zeros(nd, np.complex64), np.zeros(nd, np.float32)
+    if nd:
+        _arg_check(_L.orion_ofdm_sc_metric_host(iq.ctypes.data, iq.size, float(fs), C.byref(pc), a, b, p.ctypes.data,
+                                                r.ctypes.data))
+    return p, r
+
+
+def earliest_accepted(results, score_threshold, cluster_len):
+    """earliest_accepted (sync/ofdm_sync.rs:488-503): of ofdm_sync's ranked results with score >=
+    score_threshold, the best-ranked one within cluster_len of the earliest; None without one."""
+    results = list(results)
+    arr = np.zeros(max(len(results), 1), _SYNC_RESULT)
+    for k, r in enumerate(results):
+        arr[k] = (r.start_sample, r.cfo_hz, r.integer_cfo_bins, r.score, 0)
+    idx = C.c_int64(-1)
+    _arg_check(_L.orion_ofdm_earliest_accepted(arr.ctypes.data, len(results), float(score_threshold), int(cluster_len),
+                                               C.byref(idx)))
+    return results[idx.value] if idx.value >= 0 else None
+
+
+def ofdm_integer_cfo(iq, fs, n_fft, cp_len, training_start, fractional_cfo_hz, corr=False):
+    """estimate_integer_cfo_bins (sync/ofdm_sync.rs:513-562) on the host: the training symbol at
+    training_start rotated by -fractional_cfo_hz, transformed at the CP boundary and correlated
+    with the known pattern over the shifts -n_fft/2 .. n_fft/2; the lowest shift wins a tie.
+    With corr, also |corr|^2 per shift (float32, n_fft + 1)."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    bins, c2 = C.c_int32(0), np.zeros(int(n_fft) + 1, np.float32)
+    _arg_check(_L.orion_ofdm_integer_cfo_host(iq.ctypes.data, iq.size, float(fs), int(n_fft), int(cp_len),
+                                              int(training_start), float(fractional_cfo_hz), C.byref(bins), c2.ctypes.data))
+    return (int(bins.value), c2) if corr else int(bins.value)
+
+
+_SYNC_BATCH_KEYS = (("p", "complex64", None), ("r", "float32", None), ("score", "float32", None), ("cfo_hz", "float32", None),
+                    ("r_peak", "float32", 1), ("top_start", "int32", OFDM_SYNC_TOP), ("top_bins", "int32", OFDM_SYNC_TOP),
+                    ("accepted_start", "int32", 1), ("accepted_in_top", "int32", 1), ("accepted_bins", "int32", 1),
+                    ("accepted_score", "float32", 1), ("accepted_cfo_hz", "float32", 1))
+_acquire_handles = {}
+
+
+def _acquire_handle(pc):
+    key = (pc.num_repeats, pc.repeat_len, pc.training, pc.training_n_fft, pc.training_cp_len)
+    if key not in _acquire_handles:
+        h = _L.orion_ofdm_acquire_new(C.byref(pc))
+        if not h:
+            raise ValueError(_err())
+        _acquire_handles[key] = h
+    return _acquire_handles[key]
+
+
+def ofdm_sync_batch(iq, fs, preamble, search_start, search_end, score_threshold=0.5, stream=None) -> dict:
+    """ofdm_sync and earliest_accepted for every row of iq (ncap, n) on the GPU, one independent
+    search per capture. Returns, per offset of the range (nd = min(search_end, n - total_len) -
+    search_start): p complex64, r, score (-1 at an offset ofdm_sync skips) and cfo_hz float32,
+    each (ncap, nd); per capture: r_peak, top_start and top_bins (ncap, 5) int32 (the first five
+    of ofdm_sync's ranking with their integer offsets; -1 / 0 padded), accepted_start (what
+    earliest_accepted(ofdm_sync(..), score_threshold, preamble.total_len) picks; -1: none),
+    accepted_in_top (which of the five it is, or -1), accepted_integer_cfo_bins (its top-five
+    entry, or 0, as the reference searches the first five only), accepted_score and
+    accepted_cfo_hz. p, r, score and the choices carry the host's bits; cfo_hz is the device's
+    atan2 (a few ulp from the host's). numpy in -> numpy out; a contiguous 2-D complex64 CUDA
+    tensor stays resident, queued on torch's current stream or on stream. The input must be
+    finite: NaN and infinities are ordered as the reference orders them on the host only."""
+    import torch
+
+    if not _is_torch(iq):
+        if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != 2:
+            raise ValueError("iq: expected a 2-D complex64 array")
+        out = ofdm_sync_batch(torch.from_numpy(np.ascontiguousarray(iq)).cuda(), fs, preamble, search_start, search_end,
+                              score_threshold, stream)
+        if stream is not None:
+            torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+    if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+        raise ValueError("iq: expected a contiguous 2-D complex64 CUDA tensor")
+    pc = _preamble_c(preamble)
+    a, b = _search_range(search_start, search_end)
+    ncap, n = int(iq.shape[0]), int(iq.shape[1])
+    nd = int(_L.orion_ofdm_sync_offsets(n, float(fs), C.byref(pc), a, b))
+    with _TorchOn(iq, stream):
+        out, fill = {}, {"top_start": -1, "accepted_start": -1, "accepted_in_top": -1}
+        for k, dt, w in _SYNC_BATCH_KEYS:
+            shape = (ncap, nd) if w is None else (ncap,) if w == 1 else (ncap, w)
+            out[k] = torch.full(shape, fill.get(k, 0), dtype=getattr(torch, dt), device=iq.device)
+        if nd and ncap:
+            oc = _SyncOutC(*[out[k].data_ptr() for k, _, _ in _SYNC_BATCH_KEYS])
+            _arg_check(_L.orion_ofdm_sync_batch_device(_acquire_handle(pc), iq.data_ptr(), ncap, n, float(fs), a, b,
+                                                       float(score_threshold), C.byref(oc), SyncEngine._stream(iq, stream)))
+    out["accepted_integer_cfo_bins"] = out.pop("accepted_bins")
+    return out
+
+
+# ---- the OFDM burst receiver: acquisition, carrier correction, training equalizer, phase tracker
+# (src/demodulate/ofdm_frame.rs:55-274, :862-1090, :1280-1592) ----
+for _name, _args in (("orion_ofdm_rotate_block_host", [C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+                     ("orion_ofdm_cpe_host", [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t]),
+                     ("orion_ofdm_soft_demap_equalized_host", [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p]),
+                     ("orion_ofdm_acquire_correct_device", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float,
+                                                            C.c_size_t, C.POINTER(_SyncOutC), C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p]),
+                     ("orion_ofdm_acquire_weights_device", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                            C.c_void_p, C.c_void_p]),
+                     ("orion_ofdm_equalize_track_device", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p])):
+    getattr(_L, _name).restype = C.c_int
+    getattr(_L, _name).argtypes = _args
+__all__ += ["ofdm_rotate_block", "ofdm_remove_common_phase_error", "BurstStep", "OfdmBurstDemod", "OfdmFrameStreamDemod"]
+
+
+def ofdm_rotate_block(iq, freq_hz, fs) -> np.ndarray:
+    """Rotator(freq_hz, fs).rotate_block(iq) from a fresh oscillator (dsp/rotator.rs:74-84), host only."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    out = np.zeros(iq.size, np.complex64)
+    _check(_L.orion_ofdm_rotate_block_host(float(freq_hz), float(fs), iq.ctypes.data, iq.size, out.ctypes.data))
+    return out
+
+
+def ofdm_remove_common_phase_error(constellation, syms) -> np.ndarray:
+    """remove_common_phase_error (demodulate/ofdm_frame.rs:200-274) over complex64 (n_sym, n_data)
+    equalized symbols, host only: unchanged below 4 symbols; else the decision-directed loop and
+    the least-squares phase ramp taken out per symbol."""
+    if not isinstance(syms, np.ndarray) or syms.dtype != np.complex64 or syms.ndim != 2:
+        raise ValueError("syms: expected a 2-D complex64 array")
+    out = np.ascontiguousarray(syms).copy()
+    _arg_check(_L.orion_ofdm_cpe_host(_ofdm_order(constellation), out.ctypes.data, out.shape[0], out.shape[1]))
+    return out
+
+
+class BurstStep:
+    """One decoded step of the burst receiver (FrameStep::Decoded with the frame's diagnostics):
+    packet (a FramePacket) or error (an RxError), consume_to (samples of the buffer this step
+    is done with), cfo_hz (the total carrier offset corrected, float32), timing_offset_samples,
+    sync_score, and, for a packet, inner_ok / outer_ok / crc_ok. symbols: the payload's equalized
+    symbols after the phase tracker (None on the path without a training symbol)."""
+
+    def __init__(self, packet, error, consume_to, cfo_hz, timing_offset_samples, sync_score, inner_ok=None, outer_ok=None,
+                 crc_ok=None, symbols=None):
+        self.packet, self.error, self.consume_to = packet, error, int(consume_to)
+        self.cfo_hz, self.timing_offset_samples, self.sync_score = np.float32(cfo_hz), int(timing_offset_samples), np.float32(sync_score)
+        self.inner_ok, self.outer_ok, self.crc_ok, self.symbols = inner_ok, outer_ok, crc_ok, symbols
+
+
+class OfdmBurstDemod(OfdmFrameDemod):
+    """The burst receiver at an unknown start (try_one_frame, demodulate/ofdm_frame.rs:1463-1592):
+    ofdm_sync over the whole buffer, earliest_accepted at score_threshold, the carrier offset
+    cfo_hz + bins fs / n_fft taken out by a Rotator from the preamble's start, the channel from
+    the training symbol at the data window, then the frame body through the held equalizer and
+    the phase tracker (decode_frame_body with a channel estimate). Without a training symbol the
+    body takes the known-start path. receive is the library's host code."""
+
+    def __init__(self, cfg, mcs_table, preamble, score_threshold=0.5):
+        super().__init__(cfg, mcs_table)
+        if not isinstance(preamble, OfdmPreamble):
+            raise ValueError("preamble: an OfdmPreamble")
+        if preamble.training is not None and preamble.training != (cfg.n_fft, cfg.cp_len):
+            raise ValueError("the training symbol must have the plan's n_fft and cp_len")
+        self.preamble, self.score_threshold = preamble, float(score_threshold)
+        self.n_fft, self.cp_len, self.fs = cfg.n_fft, cfg.cp_len, cfg.fs
+
+    def _window_start(self):
+        return self.cp_len - min(self.cfg.rx_window_backoff, self.cp_len)
+
+    def _channel_host(self, corrected):
+        """estimate_channel (:1576-1592): the training symbol's transform at the data window."""
+        if self.preamble.training is None:
+            return None
+        t0 = self.preamble.num_repeats * self.preamble.repeat_len
+        if corrected.size < t0 + self.n_fft + self.cp_len:
+            return None
+        w0 = t0 + self._window_start()
+        return fft_host(np.ascontiguousarray(corrected[w0:w0 + self.n_fft]), self.n_fft)
+
+    def _demap_host(self, constellation, iq, n_sym, est):
+        """soft_demap: (llrs, symbols) or None for too few samples."""
+        if iq.size < n_sym * self.sps:
+            return None
+        if est is None:
+            return self._llrs_host(constellation, iq, n_sym), None
+        order = _ofdm_order(constellation)
+        syms = np.zeros(n_sym * self.n_data, np.complex64)
+        llr = np.zeros(syms.size * (1, 2, 4, 6, 8)[order], np.float32)
+        x = np.ascontiguousarray(iq[:n_sym * self.sps])
+        _arg_check(_L.orion_ofdm_soft_demap_equalized_host(self.cfg._h, order, x.ctypes.data, n_sym, est.ctypes.data,
+                                                           syms.ctypes.data, llr.ctypes.data))
+        return llr, syms.reshape(n_sym, self.n_data)
+
+    def _body_host(self, body, est):
+        """decode_frame_body (:862-1090): None (incomplete), an RxError, or (packet, consumed,
+        outcome, symbols)."""
+        nh = self.header_symbols
+        got = self._demap_host(HEADER_CONSTELLATION, body, nh, est)
+        if got is None:
+            return None
+        try:
+            header = decode_chain(got[0], HEADER_FIELD_BYTES, self.header_scheme, 0, "sum_product")
+        except RxError as e:
+            return e
+        if not header.is_valid():
+            return RxError("header_crc_mismatch")
+        mcs_index, payload_len, seq, flags, seed = unpack_header_fields(header.bytes)
+        mcs = self.mcs_table.get(mcs_index)
+        if mcs is None:
+            return RxError("malformed_header")
+        sch = self.scheme(mcs)
+        try:
+            plan = block_plan(payload_len, sch)
+        except ValueError:
+            return RxError("malformed_header")
+        n_sym = self.payload_symbols(mcs, plan)
+        got = self._demap_host(mcs.constellation, body[nh * self.sps:], n_sym, est)
+        if got is None:
+            return None
+        try:
+            out = decode_chain(got[0], payload_len, sch, seed, self.f["ldpc_decode_rule"])
+        except RxError as e:
+            return e
+        if not out.is_valid():
+            return RxError("crc_mismatch")
+        return FramePacket(FrameMetadata(seq, mcs_index, flags), out.bytes[:payload_len]), (nh + n_sym) * self.sps, out, got[1]
+
+    def receive(self, iq):
+        """try_one_frame on complex64 iq: None for "need more" (fewer than pre_len + n_fft + cp
+        samples, no accepted candidate, or a body that has not fully arrived), else a BurstStep:
+        a packet with consume_to = start + pre_len + the body's samples, or an RxError with
+        consume_to = min(start + pre_len, len). NaN and infinities are handled as the reference
+        handles them here, on the host only."""
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        pre_len = self.preamble.total_len
+        if iq.size < pre_len + self.n_fft + self.cp_len:
+            return None
+        best = earliest_accepted(ofdm_sync(iq, self.fs, self.preamble, 0, iq.size), self.score_threshold, pre_len)
+        if best is None:
+            return None
+        spacing = np.float32(self.fs) / np.float32(self.n_fft)
+        total = np.float32(best.cfo_hz + np.float32(np.float32(best.integer_cfo_bins) * spacing))
+        corrected = ofdm_rotate_block(np.ascontiguousarray(iq[best.start_sample:]), -total, self.fs)
+        est = self._channel_host(corrected)
+        if corrected.size < pre_len:
+            return None
+        got = self._body_host(corrected[pre_len:], est)
+        if got is None:
+            return None
+        if isinstance(got, RxError):
+            return BurstStep(None, got, min(best.start_sample + pre_len, iq.size), total, best.start_sample, best.score)
+        packet, consumed, out, syms = got
+        consume_to = best.start_sample + pre_len + consumed
+        if consume_to > iq.size:
+            return None
+        return BurstStep(packet, None, consume_to, total, best.start_sample, best.score, out.inner_ok, out.outer_ok,
+                         out.crc_ok, syms)
+
+
+    def receive_frames(self, iq, stream=None, debug=False) -> dict:
+        """receive for every row of iq (ncap, n) on the GPU: the earliest accepted frame of each
+        capture. The launches: ofdm_sync_batch (metric, select, integer offset), the carrier
+        correction of every capture from its accepted start, the equalizer weights from the
+        corrected training symbols; then what decode_frames does, with the equalizer and the
+        phase tracker between the demodulator and the LLRs and each row's own sample count in
+        place of the row length. Per capture, numpy arrays: status (-1 need more, 0 decoded, else
+        the RX_ERRORS code), start_sample (-1: nothing accepted), cfo_hz (the total offset
+        corrected), sync_score, consume_to (as receive reports it; 0 with status -1), and
+        decode_frames' fields (error is status with -1 as 0). debug=True adds corrected (ncap, n)
+        and weights (ncap, n_fft) as they are on the device and symbols, per capture the payload's
+        equalized symbols after the phase tracker (None where no payload was demodulated). The
+        preamble must carry a training symbol, and decode_frames' limits hold (no TX low-pass,
+        the interleavers it refuses). The input must be finite: NaN and infinities are handled
+        as the reference handles them by receive, on the host, only. numpy or a contiguous torch
+        CUDA tensor, queued on torch's current stream or on stream."""
+        import torch
+
+        self._device_ok()
+        if self.preamble.training is None:
+            raise ValueError("receive_frames needs a training symbol in the preamble (receive takes either)")
+        if not _is_torch(iq):
+            if not isinstance(iq, np.ndarray) or iq.dtype != np.complex64 or iq.ndim != 2:
+                raise ValueError("iq: expected a 2-D complex64 array")
+            out = self.receive_frames(torch.from_numpy(np.ascontiguousarray(iq)).cuda(), stream, debug)
+            if debug:
+                if stream is not None:
+                    torch.cuda.synchronize()
+                out["corrected"], out["weights"] = out["corrected"].cpu().numpy(), out["weights"].cpu().numpy()
+            return out
+        if not iq.is_cuda or not iq.is_contiguous() or iq.dtype != torch.complex64 or iq.dim() != 2:
+            raise ValueError("iq: expected a contiguous 2-D complex64 CUDA tensor")
+        ns, n = int(iq.shape[0]), int(iq.shape[1])
+        pre, pre_len = self.preamble, self.preamble.total_len
+        out = {"status": np.full(ns, -1, np.int64), "start_sample": np.full(ns, -1, np.int64),
+               "cfo_hz": np.zeros(ns, np.float32), "sync_score": np.zeros(ns, np.float32), "consume_to": np.zeros(ns, np.int64)}
+        for k in ("error", "mcs_index", "sequence_num", "flags", "payload_len"):
+            out[k] = np.zeros(ns, np.int64)
+        for k in ("inner_ok", "outer_ok", "crc_ok"):
+            out[k] = np.zeros(ns, bool)
+        out["payloads"] = [np.zeros(0, np.uint8) for _ in range(ns)]
+        if debug:
+            out["symbols"] = [None] * ns
+        pc = _preamble_c(pre)
+        if ns == 0 or n < pre_len + self.n_fft + self.cp_len or \
+                not _L.orion_ofdm_sync_offsets(n, float(self.fs), C.byref(pc), 0, n):
+            if debug:
+                out["corrected"] = torch.zeros((ns, n), dtype=torch.complex64, device=iq.device)
+                out["weights"] = torch.zeros((ns, self.n_fft), dtype=torch.complex64, device=iq.device)
+            return out
+        sptr = SyncEngine._stream(iq, stream)
+        with _TorchOn(iq, stream):
+            sync = ofdm_sync_batch(iq, self.fs, pre, 0, n, self.score_threshold, stream)
+            rows = torch.empty((ns, n), dtype=torch.complex64, device=iq.device)
+            avail = torch.empty(ns, dtype=torch.int32, device=iq.device)
+            total = torch.empty(ns, dtype=torch.float32, device=iq.device)
+            weights = torch.empty((ns, self.n_fft), dtype=torch.complex64, device=iq.device)
+            oc = _SyncOutC(**{k: sync["accepted_integer_cfo_bins" if k == "accepted_bins" else k].data_ptr()
+                              for k, _, _ in _SYNC_BATCH_KEYS})
+            h = _acquire_handle(pc)
+            _arg_check(_L.orion_ofdm_acquire_correct_device(h, iq.data_ptr(), ns, n, float(self.fs), self.n_fft, C.byref(oc),
+                                                            rows.data_ptr(), avail.data_ptr(), total.data_ptr(), sptr))
+            _arg_check(_L.orion_ofdm_acquire_weights_device(h, rows.data_ptr(), ns, n, self._window_start(),
+                                                            weights.data_ptr(), sptr))
+            kept = []
+
+            def llr_of(constellation, block, idx):
+                dem = self.demod(constellation)
+                raw = ofdm_demodulate_batch(dem, block, bits=False, llr=False, stream=stream)[0]
+                w = weights if idx is None else weights.index_select(0, idx).contiguous()
+                syms, llr = dem.equalize_track(raw, w, block.shape[1] // self.sps, stream=stream)
+                if idx is not None and debug:
+                    kept.append((idx, syms))
+                return llr
+
+            res, incomplete = self._decode_rows(rows[:, pre_len:], stream, llr_of, torch.clamp(avail - pre_len, min=0))
+            if stream is not None:
+                torch.cuda.current_stream(iq.device).synchronize()
+            facts = torch.stack([sync["accepted_start"].to(torch.float64), total.to(torch.float64),
+                                 sync["accepted_score"].to(torch.float64)], dim=1).cpu().numpy()
+        start = facts[:, 0].astype(np.int64)
+        found = start >= 0
+        out["start_sample"] = start
+        out["cfo_hz"], out["sync_score"] = facts[:, 1].astype(np.float32), facts[:, 2].astype(np.float32)
+        done = found & ~incomplete
+        for k in ("error", "mcs_index", "sequence_num", "flags", "payload_len", "inner_ok", "outer_ok", "crc_ok"):
+            out[k][done] = res[k][done]
+        out["status"][done] = res["error"][done]
+        failed = done & (res["error"] != 0)
+        out["consume_to"][failed] = np.minimum(start[failed] + pre_len, n)
+        good = done & (res["error"] == 0)
+        for mi, plen in {(int(a), int(b)) for a, b in zip(res["mcs_index"][good], res["payload_len"][good])}:
+            mcs = self.mcs_table.get(mi)
+            n_sym = self.payload_symbols(mcs, block_plan(plen, self.scheme(mcs)))
+            sel = good & (res["mcs_index"] == mi) & (res["payload_len"] == plen)
+            out["consume_to"][sel] = start[sel] + pre_len + (self.header_symbols + n_sym) * self.sps
+        for c in np.flatnonzero(good):
+            out["payloads"][c] = res["payloads"][c]
+        if debug:
+            out["corrected"], out["weights"] = rows, weights
+            for idx, syms in kept:
+                sy = syms.cpu().numpy()
+                for j, c in enumerate(idx.cpu().numpy()):
+                    out["symbols"][int(c)] = sy[j].reshape(-1, self.n_data)
+        return out
+
+
+class OfdmFrameStreamDemod:
+    """OfdmFrameStreamDemod (demodulate/ofdm_frame.rs:1280-1460) on the host: a sample buffer
+    drained front to back by OfdmBurstDemod.receive. feed and flush return the BurstSteps that
+    completed, in order; every step's consume_to samples leave the buffer. evm_db, the error
+    rates, the channel estimate and the probe of the reference are not built."""
+
+    def __init__(self, cfg, mcs_table, preamble):
+        self._demod = OfdmBurstDemod(cfg, mcs_table, preamble)
+        self._buf = np.zeros(0, np.complex64)
+
+    def with_score_threshold(self, t) -> "OfdmFrameStreamDemod":
+        self._demod.score_threshold = float(t)
+        return self
+
+    def __len__(self):
+        return int(self._buf.size)
+
+    def len(self) -> int:
+        return int(self._buf.size)
+
+    def is_empty(self) -> bool:
+        return self._buf.size == 0
+
+    def clear(self):
+        self._buf = np.zeros(0, np.complex64)
+
+    def feed(self, iq) -> list:
+        self._buf = np.concatenate([self._buf, _ofdm_arr(iq, np.complex64, "iq")])
+        return self.flush()
+
+    def flush(self) -> list:
+        out = []
+        while True:
+            step = self._demod.receive(self._buf)
+            if step is None:
+                return out
+            self._buf = np.ascontiguousarray(self._buf[step.consume_to:])
+            out.append(step)
