@@ -419,3 +419,173 @@ def receive_cases(frame_of, total, pre_len, sps):
     cases["header"] = (impair(bad, 33, 12000.0, 2.9, SIGMA, 602, total=total), 33)
     cases["longer"] = (impair(frame_of(4, 11, RFm.payload(40, 92), True), 60, 8000.0, 1.1, SIGMA, 603, total=total), None)
     return cases
+
+
+# ---- exact-arithmetic captures: every Schmidl & Cox product and partial sum an integer ---------
+def int_pattern():
+    """32 Gaussian integers with parts in -3..3, the repeat of the crafted captures."""
+    rng = np.random.default_rng(3)
+    return (rng.integers(-3, 4, 32) + 1j * rng.integers(-3, 4, 32)).astype(np.complex64)
+
+
+def int_noise(n, seed):
+    """n Gaussian integers with parts in -9..9 from a seeded generator: no structure, no ties to speak of."""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(-9, 10, n) + 1j * rng.integers(-9, 10, n)).astype(np.complex64)
+
+
+def _z(n):
+    return np.zeros(n, np.complex64)
+
+
+def sc_sums_exact(iq, pre, start, end):
+    """(p_re, p_im, r, bound) in int64 per offset of [start, end) for a capture of Gaussian
+    integers, by differences of running sums (not sc_sums' walk). bound is the energy of the
+    whole window of an offset, which no partial sum of p or r exceeds in magnitude; below 2^24
+    every f32 product and partial sum of the walk is exact, in any order."""
+    num, rl, _ = pre
+    iq = np.asarray(iq)
+    re, im = np.rint(iq.real).astype(np.int64), np.rint(iq.imag).astype(np.int64)
+    assert np.array_equal(re, iq.real) and np.array_equal(im, iq.imag), "integer parts only"
+    span = (num - 1) * rl
+
+    def run(v):
+        return np.concatenate([[0], np.cumsum(v, dtype=np.int64)])
+
+    a_re, a_im, b_re, b_im = re[:-rl], im[:-rl], re[rl:], im[rl:]
+    pr, pi, en = run(a_re * b_re + a_im * b_im), run(a_re * b_im - a_im * b_re), run(re * re + im * im)
+    d = np.arange(start, end)
+    return pr[d + span] - pr[d], pi[d + span] - pi[d], en[d + rl + span] - en[d + rl], int((en[d + rl + span] - en[d]).max())
+
+
+def plateau_capture():
+    """Silence, ten repeats of the pattern, twelve at twice the amplitude, silence: 814 samples."""
+    pat = int_pattern()
+    return np.concatenate([_z(70), np.tile(pat, 10), np.tile(2 * pat, 12), _z(40)]).astype(np.complex64)
+
+
+def threshold_capture():
+    """The pattern, then the pattern doubled, at 40: the score there is exactly 1/4."""
+    pat = int_pattern()
+    return np.concatenate([_z(40), pat, 2 * pat, _z(300)]).astype(np.complex64)
+
+
+def cluster_capture(gap, total=700):
+    """The quarter-score pair at 40 and a full-score pair (3 pat | 3 pat) at 40 + gap."""
+    pat = int_pattern()
+    x = _z(total)
+    x[40:104] = np.concatenate([pat, 2 * pat])
+    x[40 + gap:40 + gap + 64] = np.concatenate([3 * pat, 3 * pat])
+    return x
+
+
+def one_sample_capture():
+    """One non-zero sample in 300: under the preamble (2, 2) exactly two offsets hold energy."""
+    x = _z(300)
+    x[100] = 3 - 2j
+    return x
+
+
+def half_band(x):
+    """x times (-1)^n, exact in f32: a carrier offset of half the sample rate."""
+    s = np.where(np.arange(len(x)) % 2 == 0, np.float32(1), np.float32(-1))
+    out = np.empty(len(x), np.complex64)
+    out.real, out.imag = np.asarray(x).real * s, np.asarray(x).imag * s
+    return out
+
+
+def crafted_cases():
+    """name -> (preamble, capture, score threshold, the facts the capture was built for). The
+    facts are asserted on the restatement (crafted_facts) before anything is held to them."""
+    p, pt, p2 = (2, 32, None), (2, 32, (64, 8)), (2, 2, None)
+    above = float(np.nextafter(F(0.25), F(1)))
+    return {
+        # the top five are the first offsets wholly inside the louder plateau; 390 .. 710 tie at key 1, so the
+        # winners (lanes 134 .. 138 of a 256-wide sweep) tie with offsets in lower lanes, 512 and up
+        "plateau": (p, plateau_capture(), 0.5, dict(nd=750, kept=735, top=[390, 391, 392, 393, 394], top_keys=[1.0] * 5,
+                                                    accepted=70, accepted_rank=374, tied_at_best=321)),
+        "threshold_met": (p, threshold_capture(), 0.25, dict(accepted=40, accepted_score=0.25)),
+        "threshold_missed": (p, threshold_capture(), above, dict(accepted=None, score_at={40: 0.25})),
+        # the second burst starts 135 / 136 past the earliest accepted offset (40), the cluster is 136 long
+        "cluster_inside": (pt, cluster_capture(135), 0.25, dict(accepted=175, accepted_score=1.0, score_at={40: 0.25})),
+        "cluster_edge": (pt, cluster_capture(136), 0.25, dict(accepted=175, score_at={40: 0.25, 176: 1.0}, top=[176, 177, 178, 179, 180])),
+        "two_kept": (p2, one_sample_capture(), 0.5, dict(kept=2, top=[97, 98, -1, -1, -1], accepted=None, r_peak=13.0,
+                                                        score_at={97: 0.0, 98: 0.0})),
+        "two_kept_threshold_0": (p2, one_sample_capture(), 0.0, dict(kept=2, accepted=97, accepted_score=0.0)),
+        "all_zero": (p2, _z(300), 0.5, dict(kept=0, top=[-1] * 5, accepted=None, r_peak=0.0)),
+    }
+
+
+def crafted_facts(x, pre, thr, start=0, end=None, fs=1e6):
+    """What the restatement alone says of capture x: nd, kept, r_peak, top (five starts, -1
+    padded), top_keys, tied_at_best (how many offsets share the best key), accepted (start or
+    None), accepted_score, accepted_rank, score_at (start -> score)."""
+    end = len(x) if end is None else end
+    res, det = ofdm_sync(x, fs, pre, start, end, detail=True)
+    nd = search_end(len(x), pre, end) - start
+    if det is None:
+        return dict(nd=nd, kept=0, r_peak=0.0, top=[-1] * TOP_N, top_keys=[], tied_at_best=0, accepted=None,
+                    accepted_score=None, accepted_rank=None, score_at={})
+    _, r, kept, r_peak = det
+    score = {q[0]: float(q[3]) for q in res}
+    keys = [float(F(q[3] * F(r[q[0] - start] / r_peak))) for q in res]
+    best = earliest_accepted(res, thr, total_len(pre))
+    starts = [q[0] for q in res]
+    return dict(nd=nd, kept=int(kept.sum()), r_peak=float(r_peak), top=starts[:TOP_N] + [-1] * (TOP_N - min(TOP_N, len(res))),
+                top_keys=keys[:TOP_N], tied_at_best=keys.count(keys[0]), accepted=None if best is None else best[0],
+                accepted_score=None if best is None else float(best[3]),
+                accepted_rank=None if best is None else starts.index(best[0]), score_at=score)
+
+
+# All ones, 900 samples, preamble (2, 32): (search_start, search_end, nd). 836 offsets exist.
+ONES_RANGES = ((10, 11, 1), (0, 4, 4), (831, 2000, 5), (0, 6, 6), (3, 258, 255), (0, 256, 256), (7, 264, 257), (0, 513, 513))
+
+
+def ones_facts(start, nd):
+    """Every offset has p = r = 32, score 1 and key 1: the ranking is the offsets in order."""
+    top = list(range(start, start + min(nd, TOP_N))) + [-1] * (TOP_N - min(nd, TOP_N))
+    return dict(nd=nd, kept=nd, r_peak=32.0, top=top, top_keys=[1.0] * min(nd, TOP_N), tied_at_best=nd, accepted=start,
+                accepted_score=1.0, accepted_rank=0)
+
+
+# Preambles (num_repeats, repeat_len) for the metric's walk: a walk of one sample; 256 + R L = 4096
+# staged samples twice (the last launch that stages in LDS); 4099, odd repeat_len (the first that does not).
+WALKS = ((2, 1), (5, 1), (30, 128), (2, 1920), (3, 1281))
+
+
+def walk_captures(num, rl):
+    """Two captures of num rl + 301 samples (301 offsets; an odd row length where num rl is
+    even): seeded Gaussian noise, and the integer pattern tiled."""
+    n = num * rl + 301
+    rng = np.random.default_rng(1000 + num * rl)
+    noise = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.3).astype(np.complex64)
+    return {"noise": noise, "integers": np.tile(int_pattern(), n // 32 + 1)[:n].copy()}
+
+
+def assert_facts(facts, want):
+    for k, v in want.items():
+        if k == "score_at":
+            assert all(facts[k][d] == s for d, s in v.items()), (k, v, {d: facts[k].get(d) for d in v})
+        else:
+            assert facts[k] == v, (k, facts[k], v)
+
+
+# ---- two more link geometries -------------------------------------------------------------------
+GEOMETRIES = {  # name -> n_fft, cp_len, data carriers, preamble; (mcs_index, payload bytes, payload symbols) per frame
+    "128_9": (dict(n_fft=128, cp_len=9, data=np.array([i for i in range(-33, 34) if i != 0], np.int32), preamble=(2, 64)),
+              ((0, 4, 8), (2, 40, 6), (3, 300, 21))),
+    "256_16": (dict(n_fft=256, cp_len=16, data=np.array([i for i in range(-100, 101) if i != 0], np.int32), preamble=(2, 128)),
+               ((2, 40, 2), (3, 300, 7))),
+}
+
+
+def geometry_captures(frame_of, frames, total=None):
+    """One capture per (mcs_index, payload bytes, ...) of frames: name -> (capture, (mcs_index,
+    sequence_num, payload)); the frame at 77, +1234 Hz, 0.4 rad, in a capture 300 samples longer
+    than the frame, or of total samples."""
+    out = {}
+    for k, (mi, nbytes, _) in enumerate(frames):
+        data = RFm.payload(nbytes, 70 + k)
+        f = frame_of(mi, k, data)
+        out[f"mcs{mi}_{nbytes}"] = (impair(f, 77, 1234.0, 0.4, SIGMA, 12, total=total or len(f) + 300), (mi, k, data))
+    return out

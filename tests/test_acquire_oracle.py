@@ -5,7 +5,11 @@ field of every result bit for bit: four preambles (with and without a training s
 repeat length is no multiple of four), the range rules, a clean frame, frames at three offsets
 with carrier offsets of -2, 0 and 2 subcarrier spacings plus a fraction, the reference's
 two-frames-in-one-capture behaviour, receive on decisive and structural captures, the stream
-demodulator on three frames fed in chunks, and goldens."""
+demodulator on three frames fed in chunks, and goldens. Crafted captures of Gaussian integers
+(exact ties, a score on the threshold, an offset on the cluster's far edge, two kept offsets, none;
+p and r also against an int64 reference), walks of one sample and around 4096 staged samples, the
+half-band carrier offset whose two correlations tie exactly, and receive at two more geometries,
+128 / 9 with 66 carriers and 256 / 16 with 200: the inputs of tests/test_gpu_acquire_edges.py."""
 import functools
 import os
 
@@ -123,6 +127,154 @@ def test_integer_cfo_and_earliest_accepted_against_the_restatement(lib):
     # the lowest shift wins a tie: an all-zero symbol correlates to zero at every shift
     assert lib.ofdm_integer_cfo(np.zeros(200, np.complex64), FS, 64, 8, 0, 0.0) == -32 == \
         A.integer_cfo_bins(np.zeros(200, np.complex64), FS, (64, 8), 0, 0.0)
+
+
+# ---- crafted captures: exact ties, the threshold and the cluster edge, few kept offsets --------
+def lib_pre(lib, pre):
+    p = lib.OfdmPreamble(pre[0], pre[1])
+    return p.with_training_symbol(*pre[2]) if pre[2] else p
+
+
+def same_sums_exact(p, r, x, pre, start, end):
+    """p and r (float32) against the int64 reference, which must stay in f32's exact range."""
+    pr, pi, rr, bound = A.sc_sums_exact(x, pre, start, end)
+    assert bound < 2 ** 24
+    assert np.array_equal(p.real, pr.astype(np.float32)) and np.array_equal(p.imag, pi.astype(np.float32))
+    assert np.array_equal(r, rr.astype(np.float32))
+
+
+@pytest.mark.parametrize("name", list(A.crafted_cases()))
+def test_crafted_captures(lib, name):
+    """The restatement holds each capture's edge; the host agrees with it result for result, and
+    its sums are the integers they must be."""
+    pre, x, thr, want = A.crafted_cases()[name]
+    facts = A.crafted_facts(x, pre, thr)
+    A.assert_facts(facts, want)
+    lp = lib_pre(lib, pre)
+    ref = A.ofdm_sync(x, FS, pre, 0, x.size)
+    got = lib.ofdm_sync(x, FS, lp, 0, x.size)
+    same_results(got, ref)
+    p, r = lib.ofdm_sc_metric(x, FS, lp, 0, x.size)
+    same_sums_exact(p, r, x, pre, 0, facts["nd"])
+    best = lib.earliest_accepted(got, thr, lp.total_len)
+    assert (None if best is None else best.start_sample) == facts["accepted"]
+
+
+@pytest.mark.parametrize("start,end,nd", A.ONES_RANGES)
+def test_all_ones_every_offset_ties(lib, start, end, nd):
+    x, pre = np.ones(900, np.complex64), (2, 32, None)
+    facts = A.crafted_facts(x, pre, 0.5, start, end)
+    A.assert_facts(facts, A.ones_facts(start, nd))
+    got = lib.ofdm_sync(x, FS, lib_pre(lib, pre), start, end)
+    same_results(got, A.ofdm_sync(x, FS, pre, start, end))
+    assert len(got) == nd and all(q.score == 1 and q.cfo_hz == 0 for q in got)
+    assert [q.start_sample for q in got] == list(range(start, start + nd))  # a stable sort of equal keys
+    assert lib.earliest_accepted(got, 0.5, 64).start_sample == start
+    p, r = lib.ofdm_sc_metric(x, FS, lib_pre(lib, pre), start, end)
+    same_sums_exact(p, r, x, pre, start, start + nd)
+    assert (p == 32).all() and (r == 32).all()
+
+
+@pytest.mark.parametrize("num,rl", A.WALKS)
+def test_walk_lengths_against_the_restatement(lib, num, rl):
+    """A walk of one sample, and the preambles on either side of the device's staging limit."""
+    pre, lp = (num, rl, None), lib.OfdmPreamble(num, rl)
+    for kind, x in A.walk_captures(num, rl).items():
+        assert x.size == num * rl + 301
+        same_results(lib.ofdm_sync(x, FS, lp, 0, x.size), A.ofdm_sync(x, FS, pre, 0, x.size))
+        p, r = lib.ofdm_sc_metric(x, FS, lp, 0, x.size)
+        assert p.size == 301
+        if kind == "integers":
+            same_sums_exact(p, r, x, pre, 0, 301)
+
+
+def half_band_facts(lib, cfg, pre, x, start):
+    """What makes the half-band capture a tie, on the host's own values: the S&C sums and the
+    fraction are the unshifted capture's bit for bit, the two largest |corr|^2 are bit-equal at
+    -/+ n_fft / 2 and the third is at most a quarter of them. Returns the shifted capture."""
+    assert pre.repeat_len % 2 == 0
+    xh = A.half_band(x)
+    for a, b in zip(lib.ofdm_sc_metric(x, FS, pre, 0, x.size), lib.ofdm_sc_metric(xh, FS, pre, 0, x.size)):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    res, plain = lib.ofdm_sync(xh, FS, pre, 0, x.size), lib.ofdm_sync(x, FS, pre, 0, x.size)
+    assert all((a.start_sample, bits32(a.cfo_hz), bits32(a.score)) == (b.start_sample, bits32(b.cfo_hz), bits32(b.score))
+               for a, b in zip(res, plain))
+    half = cfg.n_fft // 2
+    assert res[0].start_sample == start and res[0].integer_cfo_bins == -half
+    _, c2 = lib.ofdm_integer_cfo(xh, FS, cfg.n_fft, cfg.cp_len, start + pre.num_repeats * pre.repeat_len, res[0].cfo_hz, corr=True)
+    order = np.argsort(-c2.astype(np.float64), kind="stable")
+    assert (order[:2] - half).tolist() == [-half, half] and bits32(c2[order[0]]) == bits32(c2[order[1]])
+    assert c2[order[2]] <= 0.25 * c2[order[0]]
+    return xh
+
+
+@pytest.mark.parametrize("geometry", ["64_8"] + list(A.GEOMETRIES))
+def test_half_band_offset_is_an_exact_tie_and_the_lower_shift_wins(lib, geometry):
+    cfg, t, pre, link, x, data, start = half_band_case(geometry)
+    xh = half_band_facts(lib, cfg, pre, x, start)
+    want = A.receive(link, xh)
+    assert want["error"] == 0 and np.array_equal(want["payload"], data) and want["start_sample"] == start
+    check_step(lib, lib.OfdmBurstDemod(cfg, t, pre).receive(xh), want)
+    wb, wc = A.integer_cfo_bins(xh, FS, (cfg.n_fft, cfg.cp_len), start + pre.num_repeats * pre.repeat_len,
+                                A.ofdm_sync(xh, FS, ref_pre(pre), 0, xh.size)[0][1], corr=True)
+    assert wb == -cfg.n_fft // 2 and bits32(wc[0]) == bits32(wc[-1]) == bits32(wc.max())
+
+
+@functools.lru_cache(maxsize=None)
+def half_band_case(geometry):
+    """(cfg, table, preamble, link, the capture before the shift, payload, start): a decisive
+    frame at the plan 64 / 8 or at one of the two further geometries."""
+    import orion_sdr as lib
+
+    if geometry == "64_8":
+        cfg, t, pre, link, f = frame(lib)
+        x, data, start = A.impair(f, 101, 2300.0, 1.0, A.SIGMA, 11), R.payload(40, 1), 101
+    else:
+        cfg, t, pre, link, caps = geometry_cases(geometry)
+        x, (_, _, data) = caps["mcs2_40"]
+        start = 77
+    x.flags.writeable = False
+    return cfg, t, pre, link, x, data, start
+
+
+# ---- two more link geometries ----------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def geometry_cases(geometry, common_length=False):
+    """(cfg, table, preamble, link, name -> (capture, (mcs_index, sequence_num, payload))) of
+    A.GEOMETRIES, shared with the GPU tests; with common_length every capture is as long as the
+    longest, so that they stack."""
+    import orion_sdr as lib
+
+    geo, frames = A.GEOMETRIES[geometry]
+    cfg, t, pre, link = links(lib, **geo)
+    mod = lib.OfdmFrameMod(cfg, t, pre)
+
+    def frame_of(mi, seq, data):
+        return mod.modulate_frame(lib.FramePacket(lib.FrameMetadata(seq, mi, seq % 5), data), seq)
+
+    total = 300 + max(mod.frame_len(mi, n) for mi, n, _ in frames) if common_length else None
+    caps = A.geometry_captures(frame_of, frames, total)
+    for v in caps.values():
+        v[0].flags.writeable = False
+    return cfg, t, pre, link, caps
+
+
+@pytest.mark.parametrize("geometry,k", [(g, k) for g in A.GEOMETRIES for k in range(len(A.GEOMETRIES[g][1]))])
+def test_receive_at_other_geometries(lib, geometry, k):
+    cfg, t, pre, link, caps = geometry_cases(geometry)
+    mi, nbytes, nsym = A.GEOMETRIES[geometry][1][k]
+    x, (_, seq, data) = caps[f"mcs{mi}_{nbytes}"]
+    assert x.size == lib.OfdmFrameMod(cfg, t, pre).frame_len(mi, nbytes) + 300 <= 4600
+    want = A.receive(link, x)
+    # the restatement alone decodes this capture
+    assert want is not None and want["error"] == 0 and np.array_equal(want["payload"], data) and want["start_sample"] == 77
+    assert want["symbols"].shape == (nsym, len(link.data))
+    step = lib.OfdmBurstDemod(cfg, t, pre).receive(x)
+    check_step(lib, step, want)
+    assert step.packet == lib.FramePacket(lib.FrameMetadata(seq, mi, seq % 5), data)
+    res = lib.ofdm_sync(x, FS, pre, 0, x.size)
+    same_results(res, A.ofdm_sync(x, FS, ref_pre(pre), 0, x.size))
+    assert res[0].start_sample == 77 and res[0].integer_cfo_bins == 0
 
 
 @functools.lru_cache(maxsize=None)

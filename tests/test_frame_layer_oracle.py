@@ -28,9 +28,11 @@ def table(lib, triples):
     return lib.McsTable([lib.Mcs(c, i, o) for c, i, o in triples])
 
 
-def links(lib, gain=1.0, roll_off=0, mcs=None, preamble=(2, 32), training=True, **frame):
-    """The same link for the library (cfg, table, OfdmPreamble) and the restatement."""
-    cfg = lib.OfdmConfig(64, 8, R.DATA62, Z32, ZC, 1e6, 0.0, gain, "qpsk")
+def links(lib, gain=1.0, roll_off=0, mcs=None, preamble=(2, 32), training=True, n_fft=64, cp_len=8, data=None, **frame):
+    """The same link for the library (cfg, table, OfdmPreamble) and the restatement; the plan is
+    64 / 8 with 62 data carriers unless n_fft, cp_len and data (carrier indices) say otherwise."""
+    data = R.DATA62 if data is None else np.asarray(data, np.int32)
+    cfg = lib.OfdmConfig(n_fft, cp_len, data, Z32, ZC, 1e6, 0.0, gain, "qpsk")
     if roll_off:
         cfg = cfg.with_symbol_window(roll_off)
     for k in ("outer_interleaver", "inner_interleaver"):
@@ -49,10 +51,10 @@ def links(lib, gain=1.0, roll_off=0, mcs=None, preamble=(2, 32), training=True, 
     if "ldpc_decode_rule" in frame:
         r = frame["ldpc_decode_rule"]
         cfg = cfg.with_ldpc_decode_rule(*(r if isinstance(r, tuple) else (r,)))
-    link = R.Link(64, 8, R.DATA62, gain=gain, roll_off=roll_off, mcs=mcs, preamble=preamble, training=training, **frame)
+    link = R.Link(n_fft, cp_len, data, gain=gain, roll_off=roll_off, mcs=mcs, preamble=preamble, training=training, **frame)
     pre = lib.OfdmPreamble(*preamble)
     if training:
-        pre = pre.with_training_symbol(64, 8)
+        pre = pre.with_training_symbol(n_fft, cp_len)
     return cfg, table(lib, link.mcs), pre, link
 
 
@@ -143,6 +145,33 @@ def test_modulate_and_decode_against_the_restatement(lib, idx):
                 assert np.array_equal(p.payload, data)
             noisy = R.awgn(body, 0.05 if mi < 2 else 0.02, idx)
             same_result(decoded(lib, dem, noisy), R.decode_frame(link, noisy))
+
+
+@pytest.mark.parametrize("geometry", ["128_9", "256_16"])
+def test_known_start_path_at_other_geometries(lib, geometry):
+    """128 / 9 with 66 carriers (odd samples per symbol) and 256 / 16 with 200: the header's and
+    the payload's symbol counts, the padding of the last symbol, the preamble and the frame's IQ
+    bit for bit, decode clean and noisy, window roll-off 0 and 2."""
+    import np_ref_acquire as A
+
+    geo, frames = A.GEOMETRIES[geometry]
+    for roll_off in (0, 2):
+        cfg, t, pre, link = links(lib, roll_off=roll_off, **geo)
+        mod, dem = lib.OfdmFrameMod(cfg, t, pre), lib.OfdmFrameDemod(cfg, t)
+        n_data, sps = len(geo["data"]), geo["n_fft"] + geo["cp_len"]
+        assert (mod.n_data, mod.sps, mod.header_symbols) == (n_data, sps, -(-512 // n_data)) and pre.total_len == geo["n_fft"] + sps
+        for k, (mi, nbytes, nsym) in enumerate(frames):
+            data = R.payload(nbytes, 70 + k)
+            got = mod.modulate_frame(lib.FramePacket(lib.FrameMetadata(k, mi, k % 5), data), k)
+            assert got.size == mod.frame_len(mi, nbytes) == pre.total_len + (mod.header_symbols + nsym) * sps
+            assert same32(got, R.modulate_frame(link, mi, k, k % 5, data, k)), (mi, nbytes)
+            body = got[pre.total_len:]
+            if not roll_off:
+                p = dem.decode(np.ascontiguousarray(body))
+                assert (p.metadata.mcs_index, p.metadata.sequence_num, p.metadata.flags) == (mi, k, k % 5)
+                assert np.array_equal(p.payload, data)
+            for rx in (body, R.awgn(body, 0.05 if mi < 2 else 0.02, k), body[:-1]):
+                same_result(decoded(lib, dem, rx), R.decode_frame(link, rx))
 
 
 def test_every_symbol_is_windowed_exactly_once(lib):

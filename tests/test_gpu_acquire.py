@@ -57,9 +57,10 @@ def cfo_distance(got, want, fs, repeat_len):
     return np.abs(got.astype(np.float64) - want.astype(np.float64)) / ulp.astype(np.float64)
 
 
-def check_sync(lib, pre, x, out, start, end, thr=0.5):
+def check_sync(lib, pre, x, out, start, end, thr=0.5, left_out=None):
     """Every output of ofdm_sync_batch for captures x against the host; returns the largest
-    cfo_hz distance in ulps."""
+    cfo_hz distance in ulps. left_out (a list) collects (capture, rank) of every candidate whose
+    integer offset the decisiveness guard did not compare."""
     worst = 0.0
     for c in range(len(x)):
         p, r = lib.ofdm_sc_metric(x[c], FS, pre, start, end)
@@ -85,6 +86,8 @@ def check_sync(lib, pre, x, out, start, end, thr=0.5):
                 c2 = np.sort(c2.astype(np.float64))
                 if c2[-2] <= 0.25 * c2[-1]:  # decisive on the host's own values
                     assert int(out["top_bins"][c][j]) == bins, (c, j)
+                elif left_out is not None:
+                    left_out.append((c, j))
             else:
                 assert int(out["top_bins"][c][j]) == 0
         best = lib.earliest_accepted(res, thr, pre.total_len)
@@ -238,7 +241,7 @@ def check_receive(lib, bd, link, names, x, out, symbols=True):
             row = np.ascontiguousarray(got[:src.size])
             mcs = bd.mcs_table.get(md.mcs_index)
             nsym = bd.payload_symbols(mcs, lib.block_plan(step.packet.payload.size, bd.scheme(mcs)))
-            body = row[pre_len + bd.header_symbols * 72:]
+            body = row[pre_len + bd.header_symbols * bd.sps:]
             truth = A.soft_demap_eq(link, mcs.constellation, body, nsym,
                                     A.equalizer_weights(A.estimate_channel(link, row, A.D), A.D), A.D)[1]
             host = bd._demap_host(mcs.constellation, body, nsym, bd._channel_host(row))[1]

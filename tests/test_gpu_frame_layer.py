@@ -3,8 +3,9 @@ k_frame_assemble under them) against the library's host layer (modulate_frame / 
 held to tests/np_ref_frame.py by tests/test_frame_layer_oracle.py), for equality: IQ as uint32 for
 both reference concatenations and the DVB-style one, with and without a window; every returned
 field of decode_frames on the noisy set, a corrupted header symbol, a longer table at the
-transmitter, a row cut short, and one batch mixing two MCS entries and two payload lengths; torch
-tensors in and out on a stream of the caller's."""
+transmitter, a row cut short, and one batch mixing two MCS entries and two payload lengths; both
+again at the geometries 128 / 9 / 66 carriers and 256 / 16 / 200; torch tensors in and out on a
+stream of the caller's."""
 import numpy as np
 import pytest
 
@@ -46,8 +47,9 @@ def check_frames(lib, dem, rx, out):
             sch = dem.scheme(mcs)
             n = int(out["payload_len"][k])
             nsym = dem.payload_symbols(mcs, lib.block_plan(n, sch))
-            seed = lib.unpack_header_fields(lib.decode_chain(dem._llrs_host("bpsk", rx[k], 9), 14, dem.header_scheme).bytes)[4]
-            o = lib.decode_chain(dem._llrs_host(mcs.constellation, rx[k][9 * 72:], nsym), n, sch, seed, dem.f["ldpc_decode_rule"])
+            nh = dem.header_symbols
+            seed = lib.unpack_header_fields(lib.decode_chain(dem._llrs_host("bpsk", rx[k], nh), 14, dem.header_scheme).bytes)[4]
+            o = lib.decode_chain(dem._llrs_host(mcs.constellation, rx[k][nh * dem.sps:], nsym), n, sch, seed, dem.f["ldpc_decode_rule"])
             assert (bool(out["inner_ok"][k]), bool(out["outer_ok"][k]), bool(out["crc_ok"][k])) == (o.inner_ok, o.outer_ok, o.crc_ok), k
 
 
@@ -125,6 +127,50 @@ def test_decode_frames_errors_and_grouping(gpu_lib):
     assert out["error"][0] == E["malformed_header"] and out["error"][1] == 0 and out["error"][3] == 0
     out = dem.decode_frames(np.ascontiguousarray(rx[:, :9 * 72 - 1]))  # not even a header
     assert (out["error"] == E["malformed_header"]).all()
+
+
+@pytest.mark.parametrize("geometry", ["128_9", "256_16"])
+def test_other_geometries(gpu_lib, geometry):
+    """128 / 9 with 66 data carriers (137 samples per symbol, 8 header symbols) and 256 / 16 with
+    200 (3 header symbols): modulate_frames against modulate_frame with and without a window, and
+    decode_frames on one batch mixing every frame of the geometry: clean, lightly noisy, noisy enough
+    to fail the QAM payloads, and one row drowned."""
+    import np_ref_acquire as A
+
+    lib = gpu_lib
+    geo, frames = A.GEOMETRIES[geometry]
+    rows, sent = [], []
+    for roll_off in (0, 2):
+        cfg, t, pre, _ = links(lib, roll_off=roll_off, **geo)
+        mod = lib.OfdmFrameMod(cfg, t, pre)
+        assert mod.sps == geo["n_fft"] + geo["cp_len"] and mod.n_data == len(geo["data"])
+        for mi, n, nsym in frames:
+            pay = np.stack([R.payload(n, 10 * k + mi) for k in range(3)])
+            seq, flags = np.array([0, 7, 0xFFFFFFFF], np.int64), np.array([0, 255, 3], np.int64)
+            seeds = np.array([0, 0x12345678, 0xFFFFFFFF], np.int64)
+            got = mod.modulate_frames(pay, mi, sequence_nums=seq, flags=flags, seeds=seeds)
+            assert got.dtype == np.complex64 and got.shape == (3, pre.total_len + (mod.header_symbols + nsym) * mod.sps)
+            for k in range(3):
+                f = lib.FramePacket(lib.FrameMetadata(int(seq[k]), mi, int(flags[k])), pay[k])
+                assert same32(got[k], mod.modulate_frame(f, int(seeds[k]))), (roll_off, mi, n, k)
+            if roll_off == 0:
+                rows += [R.awgn(got[k][pre.total_len:], (0.0, 0.004, 0.02)[k], 50 + k) for k in range(3)]
+                sent += [(mi, pay[k]) for k in range(3)]
+    rows.append(R.awgn(rows[0], 0.5, 60))  # drowned: no header
+    cfg, t, pre, _ = links(lib, **geo)
+    dem = lib.OfdmFrameDemod(cfg, t)
+    rx = np.zeros((len(rows), max(r.size for r in rows)), np.complex64)
+    for k, r in enumerate(rows):
+        rx[k, :r.size] = r
+    out = dem.decode_frames(rx)
+    check_frames(lib, dem, rx, out)
+    E = lib.RX_ERRORS
+    for k, (mi, pay) in enumerate(sent):
+        if k % 3 < 2:  # the clean and the lightly noisy rows decode; the third is the host's verdict, whichever
+            assert out["error"][k] == 0 and out["mcs_index"][k] == mi and np.array_equal(out["payloads"][k], pay), k
+    assert out["error"][-1] == E["header_crc_mismatch"] and (out["error"] == E["crc_mismatch"]).any()
+    cut = np.ascontiguousarray(rx[:, :min(r.size for r in rows) + 5])  # the longer frames no longer fit
+    check_frames(lib, dem, cut, dem.decode_frames(cut))
 
 
 def test_torch_tensors_on_a_stream_of_the_callers(gpu_lib):

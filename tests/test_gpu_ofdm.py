@@ -71,7 +71,7 @@ def fft_case(lib, n):
 
 
 @pytest.mark.parametrize("batch", [1, 3, 257])
-@pytest.mark.parametrize("n", [8, 16, 64, 256, 2048, 4096])
+@pytest.mark.parametrize("n", [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096])
 def test_transform_against_f64_truth(lib, n, batch):
     x257, e_host = fft_case(lib, n)
     x = np.ascontiguousarray(x257[:batch])
@@ -91,7 +91,7 @@ def test_transform_against_f64_truth(lib, n, batch):
     assert eb <= 2 * e_host[False]
 
 
-@pytest.mark.parametrize("n", [8, 16, 64, 256, 2048, 4096])
+@pytest.mark.parametrize("n", [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096])
 def test_transform_structure(lib, torch, n):
     f = lib.FftBlock(n)
     imp = np.zeros(n, np.complex64)
