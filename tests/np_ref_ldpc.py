@@ -6,7 +6,10 @@ Two restatements of ldpc_decode_soft, as elsewhere in this suite: `decode_batch`
 vectorised over a batch of codewords, and `decode_scalar`, which follows ldpc.rs:673-757
 loop for loop (m[check][bit] and e[check][bit] arrays, the 1-based padded NM / MN tables).
 Both take the check rule and return (plain, errors, iterations); test_ldpc_oracle.py holds
-them to each other and to the library's host decoder bit for bit.
+them to each other and to the library's host decoder bit for bit. `decode_batch` also takes
+operation variants (np_ref_ldpc_family.VARIANTS: one-line departures that stand in for a
+drifting device build; the default is the reference), and `knife_set` gives the words on
+which such a departure changes an output.
 
 The check rule: "reference" is ldpc.rs as written, e = -2 fast_atanh(a) for every check.
 "sum_product" is e = +2 fast_atanh(a) for the checks with 7 entries and nothing else
@@ -21,9 +24,12 @@ import functools
 
 import numpy as np
 
+import np_ref_ldpc_family as F
+
 f32 = np.float32
 N, K, M = 174, 91, 83
 RULES = ("reference", "sum_product")
+PROTOCOLS = ("ft8", "ft4")
 FT4_XOR = bytes([0x4A, 0x5E, 0x89, 0xB4, 0xB0, 0x8A, 0x79, 0x55, 0xBE, 0x28])  # ft4.rs:22
 GRAY = {"ft8": [0, 1, 3, 2, 5, 6, 4, 7], "ft4": [0, 1, 3, 2]}  # gray.rs:10,28
 BITS = {"ft8": 3, "ft4": 2}
@@ -288,11 +294,8 @@ def decode_scalar(llr, max_iter=20, rule="reference"):
 
 
 # ---------------------------------------------------------- vectorised decoder --
-def _vtanh(x):
-    x2 = x * x
-    a = x * (f32(945.0) + x2 * (f32(105.0) + x2))
-    b = f32(945.0) + x2 * (f32(420.0) + x2 * f32(15.0))
-    return np.where(x < f32(-4.97), f32(-1.0), np.where(x > f32(4.97), f32(1.0), a / b)).astype(f32)
+def _vtanh(x, variants=()):
+    return F.fast_tanh(x, variants)  # the same rational function, ldpc.rs:644-653 = ldpc_codes.rs:560-570
 
 
 def _vatanh(x):
@@ -302,59 +305,90 @@ def _vatanh(x):
     return (a / b).astype(f32)
 
 
-def decode_batch(llr, max_iter=20, rule="reference"):
+@functools.lru_cache(maxsize=None)
+def _graph():
+    """bit_of [522]: the bit of each edge; bit_edge [174, 3]: the edges of each bit in ascending
+    check order (the edge list is check-major); starts: per check weight the first edges."""
+    t = tables()
+    bit_of = t["edges"][:, 1]
+    bit_edge = np.array([np.flatnonzero(bit_of == i) for i in range(N)], np.int64)
+    starts = {nr: t["row_start"][:-1][t["num_rows"] == nr] for nr in (6, 7)}
+    return bit_of, bit_edge, starts
+
+
+def _iteration(llr, m, rule, variants=()):
+    """One iteration on [L, 174] LLRs and [L, 522] bit -> check messages: the check -> bit
+    messages per bit (e0, e1, e2, each [L, 174]), the decision sums [L, 174] and the next bit ->
+    check messages [L, 522]. variants: np_ref_ldpc_family.VARIANTS, the default is the reference."""
+    bit_of, bit_edge, starts = _graph()
+    tm = _vtanh(-m / f32(2.0), variants)
+    el = np.zeros_like(tm)
+    for nr in (6, 7):
+        idx = starts[nr][:, None] + np.arange(nr)[None, :]
+        factor = f32(2.0) if (rule == "sum_product" and nr == 7) else f32(-2.0)
+        tr = tm[:, idx]  # [L, rows, nr]
+        for p1 in range(nr):
+            a = np.ones(tr.shape[:2], f32)
+            for p2 in (range(nr - 1, -1, -1) if "prod_desc" in variants else range(nr)):
+                if p2 != p1:
+                    a = a * tr[:, :, p2]
+            el[:, idx[:, p1]] = factor * _vatanh(a)
+    e0, e1, e2 = el[:, bit_edge[:, 0]], el[:, bit_edge[:, 1]], el[:, bit_edge[:, 2]]
+    l = ((llr + e0) + e1) + e2
+    ml = np.empty_like(tm)
+    if "sum_assoc" in variants:
+        ml[:, bit_edge[:, 0]] = llr + (e1 + e2)
+        ml[:, bit_edge[:, 1]] = llr + (e0 + e2)
+        ml[:, bit_edge[:, 2]] = llr + (e0 + e1)
+    else:
+        ml[:, bit_edge[:, 0]] = (llr + e1) + e2
+        ml[:, bit_edge[:, 1]] = (llr + e0) + e2
+        ml[:, bit_edge[:, 2]] = (llr + e0) + e1
+    return (e0, e1, e2), l, ml
+
+
+def decode_batch(llr, max_iter=20, rule="reference", variants=()):
     """The same arithmetic per codeword, vectorised over a batch [B, 174] and over the
     checks of equal weight; messages live on the 522 edges. Returns (plain [B, 174] uint8,
     errors [B], iterations [B])."""
-    t = tables()
-    edges, row_start, num_rows = t["edges"], t["row_start"], t["num_rows"]
+    bit_of = _graph()[0]
     llr = np.ascontiguousarray(llr, f32).reshape(-1, N)
     nb = llr.shape[0]
-    bit_of = edges[:, 1]
-    # edges of each bit in ascending check order (the edge list is check-major)
-    bit_edge = np.array([np.flatnonzero(bit_of == i) for i in range(N)], np.int64)
-    groups = []  # (nr, edge index [rows, nr], factor)
-    for nr in (6, 7):
-        starts = row_start[:-1][num_rows == nr]
-        factor = f32(2.0) if (rule == "sum_product" and nr == 7) else f32(-2.0)
-        groups.append((nr, starts[:, None] + np.arange(nr)[None, :], factor))
     zero = f32(0.0)
     plain = (llr <= zero).astype(np.uint8)
     errors = count_errors(plain)
     iterations = np.zeros(nb, np.int64)
     live = np.flatnonzero(errors != 0)  # words still iterating
     m = llr[:, bit_of].copy()  # [B, 522]
-    e = np.zeros_like(m)
     with np.errstate(all="ignore"):
         for _ in range(max_iter):
             if len(live) == 0:
                 break
             iterations[live] += 1
-            tm = _vtanh(-m[live] / f32(2.0))
-            el = np.zeros_like(tm)
-            for nr, idx, factor in groups:
-                tr = tm[:, idx]  # [L, rows, nr]
-                for p1 in range(nr):
-                    a = np.ones(tr.shape[:2], f32)
-                    for p2 in range(nr):
-                        if p2 != p1:
-                            a = a * tr[:, :, p2]
-                    el[:, idx[:, p1]] = factor * _vatanh(a)
-            e0, e1, e2 = el[:, bit_edge[:, 0]], el[:, bit_edge[:, 1]], el[:, bit_edge[:, 2]]
-            l = ((llr[live] + e0) + e1) + e2
+            _, l, ml = _iteration(llr[live], m[live], rule, variants)
             cur = (l <= zero).astype(np.uint8)
             err = count_errors(cur)
             better = err < errors[live]
             idx_b = live[better]
             errors[idx_b] = err[better]
             plain[idx_b] = cur[better]
-            ml = np.empty_like(tm)
-            ml[:, bit_edge[:, 0]] = (llr[live] + e1) + e2
-            ml[:, bit_edge[:, 1]] = (llr[live] + e0) + e2
-            ml[:, bit_edge[:, 2]] = (llr[live] + e0) + e1
             m[live] = ml
             live = live[~(better & (err == 0))]
     return plain, errors.astype(np.int64), iterations
+
+
+def trace(llr, depth, rule="reference", variants=()):
+    """Iterations 1 .. depth on every word with no early exit: (errors [depth + 1, B], the
+    initial decision's first; (e0, e1, e2) and the decision sums [B, 174] of iteration depth)."""
+    llr = np.ascontiguousarray(llr, f32).reshape(-1, N)
+    errors = [count_errors((llr <= 0).astype(np.uint8))]
+    m = llr[:, _graph()[0]].copy()
+    e = l = None
+    with np.errstate(all="ignore"):
+        for _ in range(depth):
+            e, l, m = _iteration(llr, m, rule, variants)
+            errors.append(count_errors((l <= 0).astype(np.uint8)))
+    return np.array(errors), e, l
 
 
 # ------------------------------------------------------------------ finisher --
@@ -453,6 +487,60 @@ def batch_decoded(protocol, rule, max_iter=20):
     for a in (plain, errors, iterations):
         a.setflags(write=False)
     return plain, errors, iterations
+
+
+# --------------------------------------------------------------- knife-edge words --
+# As in np_ref_ldpc_family (which explains them): the LLR of a balanced bit is the largest
+# float32 whose decision sum in iteration `depth` is still <= 0, so that bit of `plain`, decoded
+# with max_iter = depth, reports the float32 sum of the messages that reach it to the last ulp.
+# Any of the 174 bits may be balanced, since plain shows them all.
+KNIFE_BITS = 6
+KNIFE_SIGMA = 0.5
+KNIFE_CASES = tuple((rule, depth) for rule in RULES for depth in (1, 2))
+# (protocol, rule, depth) -> the seeds of its knife words, one word per seed: from 1 upwards the
+# first six for which the restatement alone meets the conditions of tests/test_ldpc_oracle.py
+# (every requested bit holds at depth 1, at least half of them at depth 2). Under the reference
+# rule few noisy words lose unsatisfied checks in an iteration, so those seeds are far apart.
+KNIFE_SEEDS = {
+    ("ft8", "reference", 1): (2, 22, 23, 49, 53, 103), ("ft8", "reference", 2): (11, 70, 79, 147, 169, 212),
+    ("ft8", "sum_product", 1): (1, 2, 3, 4, 5, 6), ("ft8", "sum_product", 2): (2, 3, 4, 5, 6, 7),
+    ("ft4", "reference", 1): (17, 29, 38, 45, 46, 49), ("ft4", "reference", 2): (85, 88, 140, 183, 188, 274),
+    ("ft4", "sum_product", 1): (1, 2, 3, 4, 5, 6), ("ft4", "sum_product", 2): (1, 3, 4, 5, 7, 8),
+}
+
+
+def knife_words(protocol, rule, depth, seed, want=KNIFE_BITS):
+    """(word [1, 174] float32, balanced: [the bits that hold], requested: [the bits balanced])."""
+    t = tables()
+    rng = np.random.default_rng([seed, PROTOCOLS.index(protocol), depth, 78])
+    x = noisy_llr(codeword_bits(protocol, random_payload(rng)), KNIFE_SIGMA, rng)
+    check_sets = [set((t["mn"][b] - 1).tolist()) for b in range(N)]
+    bits = F.pick_disjoint(check_sets, rng.permutation(N), want)
+    for i, b in enumerate(bits):
+        nbs = [[n - 1 for n in t["nm"][c, :t["num_rows"][c]].tolist() if n - 1 != b] for c in sorted(check_sets[b])]
+        F.treat_neighbours(x, nbs, i % 3, i // 3)
+    for _ in range(1 if depth == 1 else 8):
+        _, (e0, e1, e2), _ = trace(x, depth, rule)
+        new = F.balance(e0[0, bits], e1[0, bits], e2[0, bits])
+        new = np.where(np.isnan(new), x[bits], new).astype(f32)
+        if np.array_equal(new.view(np.uint32), x[bits].view(np.uint32)):
+            break
+        x[bits] = new
+    rows = np.repeat(x[None], 1 + len(bits), axis=0)
+    for i, b in enumerate(bits):
+        rows[1 + i, b] = np.nextafter(x[b], f32(np.inf))
+    errors, _, l = trace(rows, depth, rule)
+    return x[None].copy(), [F.hold(errors, l, bits, depth)], [len(bits)]
+
+
+@functools.lru_cache(maxsize=None)
+def knife_set(protocol, rule, depth):
+    """The committed knife words of (protocol, rule, depth), read-only: (words [6, 174],
+    balanced: per word the bits that hold, requested: per word the number of bits balanced)."""
+    parts = [knife_words(protocol, rule, depth, seed) for seed in KNIFE_SEEDS[(protocol, rule, depth)]]
+    words = np.concatenate([p[0] for p in parts])
+    words.setflags(write=False)
+    return words, [p[1][0] for p in parts], [p[2][0] for p in parts]
 
 
 # -------------------------------------------------------------- encoded frames --

@@ -2,7 +2,9 @@
 orion_sdr.Ldpc) against tests/np_ref_ldpc_family.py, equal in every output: the three graphs
 as CSR arrays, encode, the syndrome weight, and decode under all three rules on the input set
 (per code and sigma 24 noisy words, then all-zero LLRs, NaN, infinities, 1e30) with max_iter
-50, 1 and 0; the paths that set must hold; the reference's own properties
+50, 1 and 0; the paths that set must hold; the knife-edge words, on which a decision reports a
+float32 sum to the last ulp, with the proof that each operation variant moves one of their
+outputs; the integer words against an int64 min-sum decoder; the reference's own properties
 (tests/unit/fec.rs:526-653); the argument errors of every entry, the device entries' before any
 launch; and the host code of both frame codes under the sanitizers as a stand-alone program."""
 import collections
@@ -137,6 +139,127 @@ def test_the_scale_of_scaled_min_sum_is_used(lib):
     assert all(np.array_equal(x, y) for x, y in zip(m, one))
     for i, want in enumerate(R.decode("n512r34", llr, 50, ("scaled_min_sum", 0.5))[:3]):
         assert np.array_equal(b[i], want)
+
+
+# ---- knife-edge words: the arithmetic to the last bit ---------------------------------------
+CASE_IDS = [f"{R.rule_id(rule)}_d{depth}" for rule, depth in R.KNIFE_CASES]
+
+
+def _differing(a, b):
+    """Words in which any of bits, unsat, iterations differs."""
+    return int(sum(any(not np.array_equal(x[w], y[w]) for x, y in zip(a, b)) for w in range(len(a[0]))))
+
+
+@pytest.mark.parametrize("case", R.KNIFE_CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("name", R.NAMES)
+def test_knife_words_meet_their_conditions_on_the_restatement_alone(name, case):
+    """Six words per code, rule and depth, 24 message bits balanced in each on pairwise disjoint
+    checks. A bit holds when its decision sum in iteration depth is <= 0 at its LLR and > 0 at
+    the next float32, and that iteration's decision is the snapshot the decoder returns. At
+    depth 1 every bit holds; at depth 2 (where a balanced LLR feeds back into the messages that
+    reach it) at least half do."""
+    rule, depth = case
+    g = R.graph(name)
+    words, balanced, requested = R.knife_set(name, rule, depth)
+    assert words.shape == (R.KNIFE_WORDS, g.n) and requested == [R.KNIFE_BITS] * R.KNIFE_WORDS
+    for held in balanced:
+        assert max(held) < g.k and len(set(held)) == len(held)
+        assert len(held) == R.KNIFE_BITS if depth == 1 else 2 * len(held) >= R.KNIFE_BITS
+        rows = [set(g.col_rows[b].tolist()) for b in held]
+        assert len(set().union(*rows)) == 3 * len(held), "balanced bits share a check"
+    bits, unsat, iters, best_iter = R.decode(name, words, depth, rule)
+    assert (iters == depth).all() and (best_iter == depth).all() and (unsat > 0).all()
+    up = words.copy()
+    for w, held in enumerate(balanced):
+        assert bits[w, held].all()  # a sum <= 0 decides 1
+        up[w, held] = np.nextafter(words[w, held], np.float32(np.inf))
+    if depth == 1:  # the messages into a bit do not depend on any balanced LLR: all at once
+        dec = R.trace(name, up, 1, rule)[2]
+        assert all((dec[w, held] > 0).all() for w, held in enumerate(balanced))
+    print(f"[knife] {name} {CASE_IDS[R.KNIFE_CASES.index(case)]}: bits held {[len(h) for h in balanced]}, "
+          f"unsat {R.trace(name, words, depth, rule)[0].T.tolist()}")
+
+
+@pytest.mark.parametrize("name", R.NAMES)
+def test_every_operation_variant_moves_an_output_of_the_knife_words(name):
+    """Non-vacuity: each one-line departure from the reference's operation list (R.VARIANTS)
+    changes bits, unsat or iterations of at least one sum-product knife word; the update sum
+    only feeds the second iteration, so its variant is held to the depth-2 words. The oracle
+    input set (125 words, max_iter 50) notices none of the five."""
+    for depth in (1, 2):
+        words = R.knife_set(name, "sum_product", depth)[0]
+        base = R.decode(name, words, depth)[:3]
+        counts = {v: _differing(base, R.decode(name, words, depth, "sum_product", (v,))[:3]) for v in R.VARIANTS}
+        print(f"[knife] {name} sum_product depth {depth}: words of {len(words)} that differ under {counts}")
+        for v in R.VARIANTS:
+            if (v == "sum_assoc") == (depth == 2):
+                assert counts[v] > 0, (name, depth, v)
+    # the min-sum words: the scale and the choice of magnitude feed the balanced sums
+    words = R.knife_set(name, ("scaled_min_sum", 0.75), 1)[0]
+    base = R.decode(name, words, 1, ("scaled_min_sum", 0.75))[:3]
+    assert _differing(base, R.decode(name, words, 1, "min_sum")[:3]) == len(words)
+    assert _differing(base, R.decode(name, words, 1, ("scaled_min_sum", float(np.nextafter(np.float32(0.75), 1))))[:3]) > 0
+
+
+@pytest.mark.parametrize("case", R.KNIFE_CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("name", R.NAMES)
+def test_host_decoder_equals_the_restatement_on_the_knife_words(lib, name, case):
+    rule, depth = case
+    words = R.knife_set(name, rule, depth)[0]
+    for max_iter in (depth, depth + 1):
+        want = R.decode(name, words, max_iter, rule)[:3]
+        got = lib.Ldpc(name).decode_soft(np.array(words), max_iter, rule)
+        for g, w, what in zip(got, want, ("bits", "unsat", "iterations")):
+            assert np.array_equal(g, w), (what, max_iter, np.argwhere(g != w)[:8])
+
+
+# ---- exact words for the min-sum rules: an int64 decoder from the definition -----------------
+@pytest.fixture(scope="module")
+def int_ref():
+    """(code, max_iter, half) -> R.int_min_sum on the code's integer words, computed once."""
+    cache = {}
+
+    def get(name, max_iter, half=False):
+        key = (name, max_iter, half)
+        if key not in cache:
+            cache[key] = R.int_min_sum(name, R.int_words(name), max_iter, R.HALF_UNIT if half else 1, half)
+        return cache[key]
+
+    return get
+
+
+@pytest.mark.parametrize("name", R.NAMES)
+def test_integer_words_hold_what_they_must(int_ref, name):
+    """On the integer reference alone: every magnitude formed stays below 2^24 (so float32 holds
+    it exactly; with scale 0.5 in units of 2^-8), and the set has equal-magnitude ties, decision
+    sums that are exactly 0, a word decoded in at most 2 iterations and a word that fails."""
+    x = R.int_words(name)
+    assert x.shape == (len(R.INT_SIGMAS) * R.INT_WORDS, R.graph(name).n) and np.abs(x).max() == 3 and (x == 0).any()
+    z = R.int_words(name, minus_zero=True)
+    assert np.array_equal(x, z) and np.signbit(z).sum() - np.signbit(x).sum() == (x == 0).sum() // 2
+    for half, max_iter in ((False, R.INT_MAX_ITER), (True, R.HALF_MAX_ITER)):
+        _, unsat, iters, max_mag, stats = int_ref(name, max_iter, half)
+        print(f"[knife] {name} integer words{' scale 0.5' if half else ''}: largest magnitude {max_mag}, {stats}, "
+              f"iterations {np.bincount(iters).tolist()}, failed {int((unsat > 0).sum())}")
+        assert max_mag < 2 ** 24
+        assert stats["ties"] > 0 and stats["zero_sums"] > 0
+        assert ((unsat == 0) & (iters >= 1) & (iters <= 2)).any() and (unsat > 0).any()
+
+
+@pytest.mark.parametrize("name", R.NAMES)
+def test_min_sum_equals_the_integer_decoder(lib, int_ref, name):
+    """The host decoder and the float32 restatement equal the int64 decoder in bits, unsat and
+    iterations: min_sum at max_iter 20, 1 and 0, scale 0.5 at max_iter 8, each on the words as
+    they are and with every second zero written as -0.0."""
+    c = lib.Ldpc(name)
+    for half, max_iter in ((False, R.INT_MAX_ITER), (False, 1), (False, 0), (True, R.HALF_MAX_ITER)):
+        rule = ("scaled_min_sum", 0.5) if half else "min_sum"
+        want = int_ref(name, max_iter, half)[:3]
+        for minus_zero in (False, True):
+            x = R.int_words(name, minus_zero)
+            for what, got in (("restatement", R.decode(name, x, max_iter, rule)[:3]), ("host", c.decode_soft(x, max_iter, rule))):
+                for g, w, field in zip(got, want, ("bits", "unsat", "iterations")):
+                    assert np.array_equal(g, w), (what, field, max_iter, half, minus_zero, np.argwhere(g != w)[:8])
 
 
 # ---- the reference's own properties (tests/unit/fec.rs:526-653) -----------------------------

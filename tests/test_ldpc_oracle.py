@@ -5,7 +5,9 @@ The batch is np_ref_ldpc.batch: 32 BPSK + noise words at each of sigma 0.4 / 0.6
 scaled to mean square 24, then the edge cases. The vectorised restatement and the
 library's host decoder and the scalar restatement (ldpc.rs loop for loop in Python
 scalars, a third of a second per word that runs 20 iterations) are all compared on every
-word under both rules."""
+word under both rules. The knife-edge words (np_ref_ldpc.knife_set) add what that batch cannot
+see: decisions that report a float32 sum to the last ulp, with the proof that each operation
+variant of the restatement moves one of their outputs."""
 import os
 import shutil
 import subprocess
@@ -144,6 +146,82 @@ def test_edge_cases(lib, rule):
         assert (it <= max_iter).all() and (it[er != 0] == max_iter).all()
         got, got_plain = _host(lib, llr, "ft8", rule, max_iter)
         assert got == R.records("ft8", pl, er, it) and np.array_equal(got_plain, pl)
+
+
+# ---- knife-edge words: the arithmetic to the last bit -----------------------------------
+KNIFE_IDS = [f"{rule}_d{depth}" for rule, depth in R.KNIFE_CASES]
+
+
+def _differing(a, b):
+    """Words in which any of plain, errors, iterations differs."""
+    return int(sum(any(not np.array_equal(x[w], y[w]) for x, y in zip(a, b)) for w in range(len(a[0]))))
+
+
+@pytest.mark.parametrize("case", R.KNIFE_CASES, ids=KNIFE_IDS)
+@pytest.mark.parametrize("protocol", PROTOCOLS)
+def test_knife_words_meet_their_conditions_on_the_restatement_alone(protocol, case):
+    """Six words per protocol, rule and depth, 6 bits balanced in each on pairwise disjoint
+    checks (with their neighbours that is most of the 174 bits). A bit holds when its decision
+    sum in iteration depth is <= 0 at its LLR and > 0 at the next float32, and that iteration's
+    decision is what the decoder returns. At depth 1 every bit holds, at depth 2 at least half.
+    The reference rule's sign depends on the check having 7 entries: bits of both kinds of
+    check are among those that hold."""
+    rule, depth = case
+    t = R.tables()
+    words, balanced, requested = R.knife_set(protocol, rule, depth)
+    assert words.shape == (6, 174) and requested == [R.KNIFE_BITS] * 6
+    weights = set()
+    for held in balanced:
+        assert len(held) == R.KNIFE_BITS if depth == 1 else 2 * len(held) >= R.KNIFE_BITS
+        checks = (t["mn"][held] - 1).ravel()
+        assert len(set(checks.tolist())) == 3 * len(held), "balanced bits share a check"
+        weights.update(t["num_rows"][checks].tolist())
+    assert weights == {6, 7}
+    plain, errors, iterations = R.decode_batch(words, depth, rule)
+    history = R.trace(words, depth, rule)[0]
+    assert (iterations == depth).all() and (errors > 0).all()
+    assert (history[depth] < history[:depth].min(axis=0)).all() and np.array_equal(errors, history[depth])
+    up = np.array(words)
+    for w, held in enumerate(balanced):
+        assert plain[w, held].all()  # a sum <= 0 decides 1
+        up[w, held] = np.nextafter(words[w, held], np.float32(np.inf))
+    if depth == 1:  # the messages into a bit do not depend on any balanced LLR: all at once
+        l = R.trace(up, 1, rule)[2]
+        assert all((l[w, held] > 0).all() for w, held in enumerate(balanced))
+    print(f"[knife] {protocol} {rule} depth {depth}: bits held {[len(h) for h in balanced]}, errors {history.T.tolist()}")
+
+
+@pytest.mark.parametrize("rule", R.RULES)
+@pytest.mark.parametrize("protocol", PROTOCOLS)
+def test_every_operation_variant_moves_an_output_of_the_knife_words(protocol, rule):
+    """Non-vacuity, for both protocols under both rules: each one-line departure from the
+    reference's operation list (np_ref_ldpc_family.VARIANTS) changes plain, errors or iterations
+    of at least one knife word. The three bit -> check sums only feed the second iteration, so
+    their variant is held to the depth-2 words, the other four to the depth-1 words. The shared
+    batch (105 words, 20 iterations) notices none of the five under either rule."""
+    for depth in (1, 2):
+        words = R.knife_set(protocol, rule, depth)[0]
+        base = R.decode_batch(words, depth, rule)
+        counts = {v: _differing(base, R.decode_batch(words, depth, rule, (v,))) for v in R.F.VARIANTS}
+        print(f"[knife] {protocol} {rule} depth {depth}: words of {len(words)} that differ under {counts}")
+        for v in R.F.VARIANTS:
+            if (v == "sum_assoc") == (depth == 2):
+                assert counts[v] > 0, (protocol, rule, depth, v)
+
+
+@pytest.mark.parametrize("case", R.KNIFE_CASES, ids=KNIFE_IDS)
+@pytest.mark.parametrize("protocol", PROTOCOLS)
+def test_host_decoder_and_scalar_restatement_equal_the_vectorised_one_on_the_knife_words(lib, protocol, case):
+    rule, depth = case
+    words = R.knife_set(protocol, rule, depth)[0]
+    for max_iter in (depth, depth + 1):
+        plain, errors, iterations = R.decode_batch(words, max_iter, rule)
+        got, got_plain = _host(lib, words, protocol, rule, max_iter)
+        assert got == R.records(protocol, plain, errors, iterations) and np.array_equal(got_plain, plain), max_iter
+    plain, errors, iterations = R.decode_batch(words, depth, rule)
+    for w in range(len(words)):
+        p, e, it = R.decode_scalar(words[w], depth, rule)
+        assert (e, it) == (int(errors[w]), int(iterations[w])) and np.array_equal(p, plain[w]), w
 
 
 # ---- the codec classes -----------------------------------------------------------------
