@@ -1,10 +1,12 @@
 """An independent numpy restatement of the OFDM symbol layer (reference src/multicarrier,
 modulate/ofdm.rs, demodulate/ofdm.rs, modulate/qam.rs, demodulate/qam.rs, sync/ofdm_sync.rs:
-270-352), f32 operation for operation, for tests/test_ofdm_oracle.py and tests/test_gpu_ofdm.py.
+270-352), f32 operation for operation, for tests/test_ofdm_oracle.py, tests/test_gpu_ofdm.py and
+tests/test_gpu_ofdm_exact.py (whose comparison rule, input sets and deliberate departures are at the end).
 
 The transform is an f32 radix-2 decimation in time of its own (the twiddles computed in
 f64 by libm and rounded once), and truth for it is numpy.fft in complex128.
 """
+import functools
 import math
 
 import numpy as np
@@ -156,43 +158,99 @@ def occupied_half_carriers(data, pilots):
 
 
 # ---- the transform --------------------------------------------------------------------------
-def twiddles(n):
+TINY = np.finfo(F).tiny
+FFT_VARIANTS = ("fma", "w0", "f32tw", "ftz", "tw_rot", "tw_rot_fused")  # departures from the host arithmetic, for the tests' own proof
+EQ_VARIANTS = ("recip", "interp_fma", "floor_strict")
+
+
+def ftz(v):
+    """Subnormals flushed to a zero of their sign."""
+    v = np.asarray(v, F)
+    return np.where(np.abs(v) < TINY, np.copysign(F(0), v), v).astype(F)
+
+
+@functools.lru_cache(maxsize=None)
+def _twiddles(n, f32):
+    if f32:  # the f32tw departure: the angle and cos / sin in f32
+        return np.array([complex(cosf(F(F(TAU * F(k)) / F(n))), -sinf(F(F(TAU * F(k)) / F(n)))) for k in range(n // 2)],
+                        np.complex64)
     return np.array([complex(F(math.cos(2.0 * math.pi * k / n)), F(-math.sin(2.0 * math.pi * k / n)))
                      for k in range(n // 2)], np.complex64)
 
 
-def bitrev(n):
+def twiddles(n, f32=False):
+    return _twiddles(int(n), bool(f32)).copy()
+
+
+@functools.lru_cache(maxsize=None)
+def _bitrev(n):
     bits = n.bit_length() - 1
     return np.array([int(format(i, f"0{bits}b")[::-1], 2) for i in range(n)])
 
 
-def fft_radix2(x, inverse=False):
+def bitrev(n):
+    return _bitrev(int(n)).copy()
+
+
+def fused_second_stages(n):
+    """The stage sizes that come second in a pass of two fused stages (a leading radix-2 pass where log2 n is odd)."""
+    cur, out = (2 if (n.bit_length() - 1) & 1 else 1), set()
+    while cur < n:
+        out.add(4 * cur)
+        cur <<= 2
+    return out
+
+
+def fft_radix2(x, inverse=False, variant=None):
     """Rows of x (..., n): f32 radix-2 decimation in time: the bit reversal, then stages of size
     2, 4, .. n, every one multiplying by its twiddle (W^0 included) as t.re = b.re w.re - b.im
     w.im, t.im = b.re w.im + b.im w.re, then a + t and a - t; the inverse conjugates the
-    twiddles and multiplies by f32(1 / n) at the end."""
+    twiddles and multiplies by f32(1 / n) at the end.
+
+    variant names one departure from that arithmetic (none of them is the library's): "fma" t.re
+    = fma(b.re, w.re, -(b.im w.im)), t.im = fma(b.re, w.im, b.im w.re); "w0" t = b where the
+    twiddle index is 0; "f32tw" the twiddles from f32 cos / sin of an f32 angle; "ftz" subnormal
+    inputs and results flushed to zero; "tw_rot" the twiddles of the upper half of every stage
+    of size >= 4 taken as -i times those a quarter stage below instead of read from the table;
+    "tw_rot_fused" the same in the second stage of each fused pair only (sizes 4, 16, 64 .. where
+    log2 n is even, 8, 32, 128 .. where it is odd), which is where a kernel that does two stages
+    per pass would make that saving."""
+    assert variant is None or variant in FFT_VARIANTS, variant
     x = np.array(x, np.complex64)
     n = x.shape[-1]
-    tw = twiddles(n)
+    tw = twiddles(n, variant == "f32tw")
     p = bitrev(n)
-    re, im = x.real.astype(F).reshape(-1, n)[:, p].copy(), x.imag.astype(F).reshape(-1, n)[:, p].copy()
+    z = ftz if variant == "ftz" else (lambda v: v)
+    re, im = z(x.real.astype(F).reshape(-1, n)[:, p]).copy(), z(x.imag.astype(F).reshape(-1, n)[:, p]).copy()
     ln = 2
-    while ln <= n:
-        half, step = ln // 2, n // ln
-        wr = tw.real[::step][:half].astype(F)
-        wi = tw.imag[::step][:half].astype(F)
+    with np.errstate(all="ignore"):
+        while ln <= n:
+            half, step = ln // 2, n // ln
+            wr = tw.real[::step][:half].astype(F)
+            wi = tw.imag[::step][:half].astype(F)
+            if half >= 2 and (variant == "tw_rot" or (variant == "tw_rot_fused" and ln in fused_second_stages(n))):
+                # -i (a + i b) = b - i a
+                q = half // 2
+                wr, wi = np.concatenate([wr[:q], wi[:q]]), np.concatenate([wi[:q], -wr[:q]])
+            if inverse:
+                wi = -wi
+            r, i = re.reshape(len(re), -1, ln), im.reshape(len(im), -1, ln)
+            ar, ai, br, bi = r[..., :half].copy(), i[..., :half].copy(), r[..., half:].copy(), i[..., half:].copy()
+            if variant == "fma":
+                wrb, wib = np.broadcast_to(wr, br.shape), np.broadcast_to(wi, br.shape)
+                tr = _fma(br, wrb, -(bi * wi).astype(F))
+                ti = _fma(br, wib, (bi * wr).astype(F))
+            else:
+                tr = z(z((br * wr).astype(F)) - z((bi * wi).astype(F)))
+                ti = z(z((br * wi).astype(F)) + z((bi * wr).astype(F)))
+            if variant == "w0":
+                tr[..., 0], ti[..., 0] = br[..., 0], bi[..., 0]
+            r[..., :half], i[..., :half] = z(ar + tr), z(ai + ti)
+            r[..., half:], i[..., half:] = z(ar - tr), z(ai - ti)
+            ln *= 2
         if inverse:
-            wi = -wi
-        r, i = re.reshape(len(re), -1, ln), im.reshape(len(im), -1, ln)
-        ar, ai, br, bi = r[..., :half].copy(), i[..., :half].copy(), r[..., half:].copy(), i[..., half:].copy()
-        tr = (br * wr).astype(F) - (bi * wi).astype(F)
-        ti = (br * wi).astype(F) + (bi * wr).astype(F)
-        r[..., :half], i[..., :half] = ar + tr, ai + ti
-        r[..., half:], i[..., half:] = ar - tr, ai - ti
-        ln *= 2
-    if inverse:
-        g = F(1.0) / F(n)
-        re, im = re * g, im * g
+            g = F(1.0) / F(n)
+            re, im = z(re * g), z(im * g)
     return cplx(re, im).reshape(x.shape)
 
 
@@ -321,14 +379,20 @@ def training_pattern(n_fft):  # sync/ofdm_sync.rs:270-272, :335-352
     return out
 
 
-def cdiv(a, b):
-    """num-complex Complex / Complex: ((a.re b.re + a.im b.im) / |b|^2, (a.im b.re - a.re b.im) / |b|^2)."""
+def cdiv(a, b, variant=None):
+    """num-complex Complex / Complex: ((a.re b.re + a.im b.im) / |b|^2, (a.im b.re - a.re b.im) / |b|^2).
+    variant "recip" (a departure, not the library's): times f32(1 / |b|^2) instead."""
     a, b = np.asarray(a, np.complex64), np.asarray(b, np.complex64)
     ar, ai, br, bi = a.real.astype(F), a.imag.astype(F), b.real.astype(F), b.imag.astype(F)
     with np.errstate(all="ignore"):
         ns = (br * br).astype(F) + (bi * bi).astype(F)
-        re = ((ar * br).astype(F) + (ai * bi).astype(F)) / ns
-        im = ((ai * br).astype(F) - (ar * bi).astype(F)) / ns
+        if variant == "recip":
+            inv = (F(1.0) / ns).astype(F)
+            re = ((ar * br).astype(F) + (ai * bi).astype(F)) * inv
+            im = ((ai * br).astype(F) - (ar * bi).astype(F)) * inv
+        else:
+            re = ((ar * br).astype(F) + (ai * bi).astype(F)) / ns
+            im = ((ai * br).astype(F) - (ar * bi).astype(F)) / ns
     return cplx(re, im)
 
 
@@ -341,18 +405,18 @@ def cmul(a, b):
     return cplx(re, im)
 
 
-def equalizer_weight(h):  # demodulate/ofdm.rs:495-502
+def equalizer_weight(h, variant=None):  # demodulate/ofdm.rs:495-502; "floor_strict" (a departure): m > floor
     h = np.atleast_1d(np.asarray(h, np.complex64))
     hr, hi = h.real.astype(F), h.imag.astype(F)
     with np.errstate(all="ignore"):
         m = (hr * hr).astype(F) + (hi * hi).astype(F)
-        ok = m >= EQUALIZER_FLOOR
+        ok = m > EQUALIZER_FLOOR if variant == "floor_strict" else m >= EQUALIZER_FLOOR
         re = np.where(ok, hr / m, F(0)).astype(F)
         im = np.where(ok, -hi / m, F(0)).astype(F)
     return cplx(re, im)
 
 
-def interpolate_at(pbins, ratios, b):  # demodulate/ofdm.rs:514-537
+def interpolate_at(pbins, ratios, b, variant=None):  # demodulate/ofdm.rs:514-537; "interp_fma" (a departure): one fma
     pbins = [int(p) for p in pbins]
     if len(pbins) == 1:
         return np.complex64(ratios[0])
@@ -365,14 +429,44 @@ def interpolate_at(pbins, ratios, b):  # demodulate/ofdm.rs:514-537
         return np.complex64(ratios[hi])
     t = F(F(b - pbins[hi - 1]) / F(pbins[hi] - pbins[hi - 1]))
     lr, ur = np.complex64(ratios[hi - 1]), np.complex64(ratios[hi])
-    re = F(lr.real) + F(F(F(ur.real) - F(lr.real)) * t)
-    im = F(lr.imag) + F(F(F(ur.imag) - F(lr.imag)) * t)
+    with np.errstate(all="ignore"):
+        if variant == "interp_fma":
+            re = _fma(F(F(ur.real) - F(lr.real)), t, F(lr.real))
+            im = _fma(F(F(ur.imag) - F(lr.imag)), t, F(lr.imag))
+        else:
+            re = F(lr.real) + F(F(F(ur.real) - F(lr.real)) * t)
+            im = F(lr.imag) + F(F(F(ur.imag) - F(lr.imag)) * t)
     return cplx(re, im)[()]
 
 
+def interpolate_bins(pbins, ratios, bins, variant=None):
+    """interpolate_at at many bins in one pass, the same operations elementwise (the tests hold
+    the two to the same bytes); what Equalizer.process uses."""
+    pb, bins = np.asarray(pbins, np.int64), np.asarray(bins, np.int64)
+    ratios = np.asarray(ratios, np.complex64)
+    if len(pb) == 1:
+        return np.full(len(bins), ratios[0], np.complex64)
+    hi = np.searchsorted(pb, bins, side="left")  # how many pilots lie below the bin
+    out = ratios[np.clip(hi, 0, len(pb) - 1)].copy()  # held past the ends, a pilot's own ratio on its bin
+    between = (hi > 0) & (hi < len(pb)) & (pb[np.clip(hi, 0, len(pb) - 1)] != bins)
+    h = hi[between]
+    t = ((bins[between] - pb[h - 1]).astype(F) / (pb[h] - pb[h - 1]).astype(F)).astype(F)
+    lr, ur = ratios[h - 1], ratios[h]
+    with np.errstate(all="ignore"):
+        dr, di = (ur.real - lr.real).astype(F), (ur.imag - lr.imag).astype(F)
+        if variant == "interp_fma":
+            re, im = _fma(dr, t, lr.real.astype(F)), _fma(di, t, lr.imag.astype(F))
+        else:
+            re, im = lr.real + (dr * t).astype(F), lr.imag + (di * t).astype(F)
+    if h.size:
+        out[between] = cplx(re, im)
+    return out
+
+
 class Equalizer:
-    def __init__(self, cfg, method):
-        self.method, self.n = method, cfg.n_fft
+    def __init__(self, cfg, method, variant=None):
+        assert variant is None or variant in EQ_VARIANTS, variant
+        self.method, self.n, self.variant = method, cfg.n_fft, variant
         order = np.argsort(cfg.pilot_bins, kind="stable")
         self.pbins, self.pvals = cfg.pilot_bins[order], cfg.pilot_val[order]
         self.dbins = cfg.data_bins.copy()
@@ -381,17 +475,17 @@ class Equalizer:
 
     def estimate_from_training_symbol(self, rx):
         if self.method == "training_symbol" and len(rx) >= self.n:
-            self.weight = equalizer_weight(cdiv(np.asarray(rx, np.complex64)[: self.n], training_pattern(self.n)))
+            self.weight = equalizer_weight(cdiv(np.asarray(rx, np.complex64)[: self.n], training_pattern(self.n),
+                                                self.variant), self.variant)
 
     def process(self, x):
         x = np.asarray(x, np.complex64)[: self.n]
         if self.method == "pilot_interp":
             if len(self.pbins):
-                ratios = cdiv(x[self.pbins], self.pvals)
-                for b in self.dbins:
-                    self.est[b] = interpolate_at(self.pbins, ratios, int(b))
+                ratios = cdiv(x[self.pbins], self.pvals, self.variant)
+                self.est[self.dbins] = interpolate_bins(self.pbins, ratios, self.dbins, self.variant)
                 self.est[self.pbins] = ratios
-            return cmul(x, equalizer_weight(self.est))
+            return cmul(x, equalizer_weight(self.est, self.variant))
         return cmul(x, self.weight)
 
 
@@ -440,3 +534,178 @@ def training_symbol(r):
     f[occ] = training_pattern(r.n_fft)[occ]
     t = fft_radix2(f, True)
     return np.concatenate([t[r.n_fft - r.cp_len:], t])
+
+
+# ---- exact comparison and the exact tests' inputs -------------------------------------------
+def _words(a):
+    """The real words of a float or complex array as unsigned integers (other dtypes: as they are)."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "c":
+        a = a.view(np.float32 if a.dtype == np.complex64 else np.float64)
+    if a.dtype.kind == "f":
+        return a, a.view(np.dtype(f"u{a.dtype.itemsize}"))
+    return None, a
+
+
+def diff_words(a, b):
+    """How many words of two arrays of one shape and dtype differ: a NaN against a NaN is no
+    difference (the host's default NaN and the device's have other payloads and signs), every
+    other word counts unless it is byte-equal, the sign of a zero or an inf included."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    fa, wa = _words(a)
+    fb, wb = _words(b)
+    if fa is None:
+        return int(np.count_nonzero(wa != wb))
+    na, nb = np.isnan(fa), np.isnan(fb)
+    return int(np.count_nonzero((na != nb) | (~na & ~nb & (wa != wb))))
+
+
+def same_bits(a, b):
+    """Equal shapes and dtypes, NaN in the same words of both, every other word byte-equal."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and diff_words(a, b) == 0
+
+
+FFT_SIZES = (8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096)
+# default_rng([seed, n]). The scaled seed is the first from 7104 up whose rows meet the overflow condition at every
+# size (7104 draws one quiet row at n = 8 that stays finite at three times the top scale).
+SET_SEEDS = {"normal": 7101, "integers": 7102, "negzero": 7103, "scaled": 7106}
+SUBNORMAL_SCALE = 2e-41  # every output word of the restatement subnormal or zero, n = 8 .. 4096
+OVERFLOW_OVER_TOP = 3.0  # overflow rows = top rows x 3: an inf in every row, under half the words NaN (found on the CPU)
+
+
+def top_scale(n):
+    return 3e38 / math.sqrt(n) / 4.0
+
+
+def input_sets(n):
+    """The transform's seeded input sets for size n: {name: (rows, n) complex64}.
+    normal: complex normal rows. integers: Gaussian integers, |re|, |im| <= 8 (exact sums, equal
+    magnitudes cancelling). negzero: a row of -0.0 - 0.0j and a row of +0.0 with a single -0.0.
+    impulse: unit impulses 1 at index 1, i at n - 1, -1 at 3 and 1 at n / 2 + 1: half of every butterfly
+    is an exact zero, so the output is the twiddle products themselves, to the last bit.
+    subnormal / top / overflow: the same three normal rows at 2e-41, at 3e38 / sqrt(n) / 4 and
+    at three times that (tests/test_ofdm_oracle.py holds the restatement's outputs to: subnormal
+    or zero; all finite; an inf in every row and at most half the words NaN)."""
+    def rng(name):
+        return np.random.default_rng([SET_SEEDS[name], n])
+
+    def normal(g, rows):
+        return g.standard_normal((rows, n)) + 1j * g.standard_normal((rows, n))
+
+    sets = {"normal": normal(rng("normal"), 4).astype(np.complex64)}
+    g = rng("integers")
+    sets["integers"] = cplx(g.integers(-8, 9, (4, n)).astype(F), g.integers(-8, 9, (4, n)).astype(F))
+    z = np.zeros((2, 2 * n), F)
+    z[0] = F(-0.0)
+    z[1, int(rng("negzero").integers(0, 2 * n))] = F(-0.0)
+    sets["negzero"] = z.view(np.complex64)
+    sets["impulse"] = np.zeros((4, n), np.complex64)
+    for row, (at, v) in enumerate(((1, 1), (n - 1, 1j), (3, -1), (n // 2 + 1, 1))):
+        sets["impulse"][row, at] = v
+    base = normal(rng("scaled"), 3)
+    for name, scale in (("subnormal", SUBNORMAL_SCALE), ("top", top_scale(n)), ("overflow", OVERFLOW_OVER_TOP * top_scale(n))):
+        with np.errstate(over="ignore"):
+            sets[name] = (base * scale).astype(np.complex64)
+        assert np.all(np.isfinite(sets[name].view(F))), (name, n)  # one inf going in is NaN everywhere coming out
+    return sets
+
+
+def cycle_rows(x, k):
+    """k rows drawn from x's in turn."""
+    return np.ascontiguousarray(x[np.arange(k) % len(x)])
+
+
+def pilot_layout(n, boost=False):
+    """(edge guard, pilot indices, pilot values) of the exact tests: n >= 32 the four pilots
+    -21, -7, 7, 21 of n_fft 64 scaled by n / 64 (out of bin order), n = 16 two pilots, n = 8
+    one; boost: the values times 4/3 (so that a division by |pilot|^2 is no division by 1)."""
+    if n >= 32:
+        idx = np.array([-(21 * n // 64), -(7 * n // 64), 7 * n // 64, 21 * n // 64], np.int32)
+        val = np.array([1, -1, 1j, 1], np.complex64)
+    elif n == 16:
+        idx, val = np.array([-3, 3], np.int32), np.array([1, -1], np.complex64)
+    else:
+        idx, val = np.array([2], np.int32), np.array([1j], np.complex64)
+    if boost:
+        val = gain(val, F(4.0) / F(3.0))
+    return n // 16, idx, val
+
+
+def floor_triplet(pval, variant=None):
+    """Three received pilot values whose estimate rx / pval has |h|^2 one ulp below
+    kEqualizerFloor, exactly on it and one ulp above it, found by search on cdiv itself."""
+    lo, hi = np.nextafter(EQUALIZER_FLOOR, F(0)), np.nextafter(EQUALIZER_FLOOR, F(1))
+    root = np.sqrt(EQUALIZER_FLOOR).astype(F)
+    hr = root
+    for _ in range(40):
+        hr = np.nextafter(hr, F(0))
+    cand_r = [hr]
+    for _ in range(80):
+        cand_r.append(np.nextafter(cand_r[-1], F(1)))
+    cand_i = np.sqrt(np.arange(0, 400) * 0.125 * float(hi - EQUALIZER_FLOOR)).astype(F)
+    h = cplx(np.repeat(np.array(cand_r, F), len(cand_i)), np.tile(cand_i, len(cand_r)))
+    rx = cmul(h, np.full(h.shape, pval, np.complex64))
+    est = cdiv(rx, np.full(h.shape, pval, np.complex64), variant)
+    m = (est.real * est.real).astype(F) + (est.imag * est.imag).astype(F)
+    out = []
+    for target in (lo, EQUALIZER_FLOOR, hi):
+        hit = np.flatnonzero(m == target)
+        assert hit.size, f"no received pilot gives |h|^2 == {target!r}"
+        out.append(rx[hit[0]])
+    return np.array(out, np.complex64)
+
+
+EQ_ROWS = {"plain": 0, "pilot_zero": 1, "crossing": 2, "floor_below": 3, "floor_on": 4, "floor_above": 5, "last": 6}
+EQ_SEED = 7201
+
+
+def equalizer_case(n, boost=False):
+    """(Config, x (7, n) complex64) for the pilot-interpolating equalizer: normal rows (std 0.7)
+    with, by EQ_ROWS: the second bin-sorted pilot (the only one at n = 8) received as exactly 0;
+    the first and second received as -0.003 and +0.004 times their values, so that the estimate
+    between them passes through 0 and |h|^2 crosses the floor twice among the data bins;
+    the first pilot's estimate with |h|^2 one ulp below the floor, on it and one ulp above it
+    (the data bins below the first pilot hold that estimate). Rows 0 and 6 are left as drawn."""
+    guard, idx, val = pilot_layout(n, boost)
+    cfg = Config(n, n // 4, contiguous_data(n, idx, guard, False), idx, val, order="qam16")
+    g = np.random.default_rng([EQ_SEED, n])
+    x = (0.7 * (g.standard_normal((7, n)) + 1j * g.standard_normal((7, n)))).astype(np.complex64)
+    order = np.argsort(cfg.pilot_bins, kind="stable")
+    pb, pv = cfg.pilot_bins[order], cfg.pilot_val[order]
+    second = min(1, len(pb) - 1)
+    x[EQ_ROWS["pilot_zero"], pb[second]] = 0
+    if len(pb) >= 2:
+        x[EQ_ROWS["crossing"], pb[0]] = gain(pv[0], F(-0.003))
+        x[EQ_ROWS["crossing"], pb[1]] = gain(pv[1], F(0.004))
+    x[[EQ_ROWS["floor_below"], EQ_ROWS["floor_on"], EQ_ROWS["floor_above"]], pb[0]] = floor_triplet(pv[0])
+    return cfg, x
+
+
+def equalizer_run(cfg, x, variant=None):
+    """The pilot-interpolating Equalizer over the rows of x on one handle: (outputs, erased),
+    erased[r, b] where row r's coefficient at bin b is 0."""
+    eq = Equalizer(cfg, "pilot_interp", variant)
+    out, erased = [], []
+    for row in x:
+        out.append(eq.process(row))
+        erased.append(equalizer_weight(eq.est, variant) == 0)
+    return np.stack(out), np.stack(erased)
+
+
+def check_equalizer_erasures(cfg, erased):
+    """What equalizer_case builds, asserted on the restatement's own erasures."""
+    pb = np.sort(cfg.pilot_bins)
+    held = cfg.data_bins if len(pb) == 1 else cfg.data_bins[cfg.data_bins < pb[0]]
+    first = np.concatenate([held, pb[:1]]).astype(np.int64)  # the bins that carry the first pilot's estimate
+    assert held.size > 0
+    assert not erased[EQ_ROWS["plain"]].any() and not erased[EQ_ROWS["last"]].any()
+    assert erased[EQ_ROWS["pilot_zero"], pb[min(1, len(pb) - 1)]]
+    assert erased[EQ_ROWS["floor_below"]][first].all()
+    assert not erased[EQ_ROWS["floor_on"]][first].any() and not erased[EQ_ROWS["floor_above"]][first].any()
+    if len(pb) >= 2:
+        between = np.sort(cfg.data_bins[(cfg.data_bins > pb[0]) & (cfg.data_bins < pb[1])]).astype(np.int64)
+        e = erased[EQ_ROWS["crossing"]][between]
+        assert e.any() and not e[0] and not e[-1]  # kept, erased, kept: the floor is crossed twice among data bins
+        assert not erased[EQ_ROWS["crossing"]][first].any()

@@ -330,6 +330,121 @@ def test_gain_inverts_and_evm(lib):
     assert lib.build_ofdm_rx_frame(c, off, bits[:-6]).evm_db is None  # the mapper comes up short
 
 
+# ---- the exact GPU tests' reference, input sets and their sharpness ---------------------------
+# tests/test_gpu_ofdm_exact.py holds the kernels to fft_host and to the restatement by R.same_bits on
+# R.input_sets; here the two references are tied to each other on those very sets, the sets are
+# shown to be what they claim, and every departure a kernel change could bring (R.FFT_VARIANTS,
+# R.EQ_VARIANTS) is shown to change at least one word of a set named below.
+NOTICED_BY = {"fma": "normal", "w0": "negzero", "f32tw": "normal", "ftz": "subnormal", "tw_rot": "impulse",
+              "tw_rot_fused": "impulse"}
+# tw_rot (W^(j + len/4) as -i W^j) reads (-0.0, -1) for the table's (6.1e-17, -1) at W^(len/4) and is the
+# table's value everywhere else. Normal, integer, subnormal and top rows never see it. The negzero rows see it
+# in every stage (tw_rot) but, placed where a kernel fusing two stages would place it (tw_rot_fused), only
+# where log2 n is even; overflow rows (inf times +-0) see tw_rot at the sizes below only. The impulse rows
+# are there for this: with one half of every butterfly an exact zero the 6.1e-17 itself comes out, at every size.
+TW_ROT_SEEN_BY_OVERFLOW = (8, 16, 32)
+
+
+def test_same_bits_rule():
+    f = np.float32
+    a = np.array([1.0, 0.0, np.inf, np.nan, 5e-42], f)
+    assert R.same_bits(a, a.copy()) and R.same_bits(a[:4].view(np.complex64), a[:4].copy().view(np.complex64))
+    quiet = a.copy()
+    quiet.view(np.uint32)[3] = 0xFFC00001  # another NaN: sign and payload are not compared
+    assert R.same_bits(a, quiet)
+    for i, v in ((1, f(-0.0)), (2, f(-np.inf)), (3, f(1.0)), (0, f(np.nan)), (4, f(0.0)), (0, np.nextafter(f(1), f(2)))):
+        b = a.copy()
+        b[i] = v
+        assert not R.same_bits(a, b) and R.diff_words(a, b) == 1
+    assert not R.same_bits(a, a.astype(np.float64)) and not R.same_bits(a, a[:4])
+    assert R.same_bits(np.arange(5, dtype=np.uint8), np.arange(5, dtype=np.uint8))
+    assert not R.same_bits(np.arange(5, dtype=np.uint8), np.arange(5, dtype=np.uint8)[::-1])
+
+
+def test_interpolation_in_one_pass_is_the_scalar_form(lib):
+    rng = np.random.default_rng(12)
+    for pb in ([5], [3, 9, 10, 40, 61], [0, 63], [7, 21, 43, 57]):
+        ratios = rand_c(rng, len(pb))
+        ratios[0] = R.cplx(-0.0, 0.0)[()]
+        bins = rng.permutation(64)
+        for variant in (None, "interp_fma"):
+            want = np.array([R.interpolate_at(pb, ratios, int(b), variant) for b in bins], np.complex64)
+            assert same(R.interpolate_bins(pb, ratios, bins, variant), want)
+        assert same(R.interpolate_bins(pb, ratios, bins), lib.ofdm_interpolate(np.array(pb, np.uint32), ratios, bins))
+
+
+@pytest.mark.parametrize("n", R.FFT_SIZES)
+def test_host_transform_is_the_restatement_on_every_input_set(lib, n):
+    for name, x in R.input_sets(n).items():
+        for inv in (False, True):
+            assert R.same_bits(lib.fft_host(x.reshape(-1), n, inv).reshape(x.shape), R.fft_radix2(x, inv)), (name, inv)
+
+
+@pytest.mark.parametrize("n", R.FFT_SIZES)
+def test_input_sets_are_what_they_claim(n):
+    s = R.input_sets(n)
+    assert list(s) == ["normal", "integers", "negzero", "impulse", "subnormal", "top", "overflow"]
+    assert np.count_nonzero(s["impulse"]) == 4 and np.all(np.abs(s["impulse"]).sum(1) == 1)
+    assert all(v.dtype == np.complex64 and v.ndim == 2 and v.shape[1] == n for v in s.values())
+    again = R.input_sets(n)
+    assert all(same(s[k], again[k]) for k in s)  # seeded
+    ints = s["integers"].view(np.float32)
+    assert np.all(ints == np.round(ints)) and np.abs(ints).max() == 8
+    z = s["negzero"].view(np.float32)
+    assert np.all(z == 0) and np.signbit(z[0]).all() and np.signbit(z[1]).sum() == 1
+    for inv in (False, True):
+        sub = R.fft_radix2(s["subnormal"], inv).view(np.float32)
+        top = R.fft_radix2(s["top"], inv).view(np.float32)
+        over = R.fft_radix2(s["overflow"], inv).view(np.float32)
+        share = (np.abs(sub) < R.TINY).mean(1)
+        print(f"[sets] n={n} inverse={inv}: subnormal-or-zero share {share.min():.4f}, nonzero {np.count_nonzero(sub)}; "
+              f"overflow rows inf {np.isinf(over).sum(1).tolist()} NaN {np.isnan(over).sum(1).tolist()} of {over.shape[1]}")
+        assert np.all(share >= 0.99) and np.count_nonzero(sub) > sub.size // 2
+        assert np.all(np.isfinite(top)) and (inv or np.abs(top).max() > 1e37)  # finite, and near the top of the range
+        assert np.all(np.isinf(over).sum(1) >= 1) and np.all(np.isnan(over).sum(1) <= over.shape[1] // 2)
+
+
+@pytest.mark.parametrize("variant", R.FFT_VARIANTS)
+def test_every_transform_departure_is_noticed_by_a_named_set(variant):
+    for n in R.FFT_SIZES:
+        s = R.input_sets(n)
+        counts = {name: [R.diff_words(R.fft_radix2(x, inv, variant), R.fft_radix2(x, inv)) for inv in (False, True)]
+                  for name, x in s.items()}
+        print(f"[sharp] {variant} n={n}: words changed forward/inverse " +
+              ", ".join(f"{k} {c[0]}/{c[1]} of {s[k].size * 2}" for k, c in counts.items()))
+        assert min(counts[NOTICED_BY[variant]]) >= 1
+        if variant == "w0":  # invisible on every input without a signed zero, as measured before these sets existed
+            assert counts["normal"] == [0, 0] and counts["integers"] == [0, 0] and counts["negzero"] == [4, 4]
+        if variant == "ftz":
+            assert all(c == [0, 0] for k, c in counts.items() if k != "subnormal")
+        if variant in ("tw_rot", "tw_rot_fused"):
+            assert all(counts[k] == [0, 0] for k in ("normal", "integers", "subnormal", "top"))
+        if variant == "tw_rot":
+            assert (min(counts["overflow"]) >= 1) == (n in TW_ROT_SEEN_BY_OVERFLOW) and min(counts["negzero"]) >= 1
+        if variant == "tw_rot_fused":  # the signed zeros alone would let it through at 8, 32, 128, 512 and 2048
+            assert (min(counts["negzero"]) >= 1) == ((n.bit_length() - 1) % 2 == 0)
+
+
+@pytest.mark.parametrize("boost", [False, True])
+@pytest.mark.parametrize("n", [8, 64, 4096])
+def test_every_equalizer_departure_is_noticed(n, boost):
+    """R.equalizer_case is what tests/test_gpu_ofdm_exact.py feeds k_ofdm_equalize. recip needs a
+    pilot whose |value|^2 is not 1 (boost); interp_fma needs two pilots (not n = 8); floor_strict
+    changes exactly the bins that carry the estimate whose |h|^2 is on the floor."""
+    cfg, x = R.equalizer_case(n, boost)
+    assert R.validate(n, cfg.data, cfg.pilot_idx) == (0, 0)
+    want, erased = R.equalizer_run(cfg, x)
+    R.check_equalizer_erasures(cfg, erased)
+    for variant in R.EQ_VARIANTS:
+        got, _ = R.equalizer_run(cfg, x, variant)
+        rows = [R.diff_words(got[i], want[i]) for i in range(len(x))]
+        print(f"[sharp] {variant} n_fft={n} boost={boost}: words changed per row {rows}")
+        can = {"recip": boost, "interp_fma": n > 8, "floor_strict": True}[variant]
+        assert (sum(rows) >= 1) == can
+        if variant == "floor_strict":
+            assert [i for i, c in enumerate(rows) if c] == [R.EQ_ROWS["floor_on"]]
+
+
 # ---- the host code under the sanitizers ---------------------------------------------------
 def test_host_code_under_address_and_undefined_sanitizers(tmp_path):
     """csrc/ofdm.cpp and tests/ofdm_host/main.cpp, built with the host compiler alone and
