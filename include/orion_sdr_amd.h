@@ -360,7 +360,23 @@ orion_block* orion_tx_lowpass_filter(const orion_tx_lowpass* t);                
  * A sync handle owns what calls reuse (step table, scratch waterfall, score map) and is
  * not a Block: there is no streaming state. One call at a time per handle.
  * Limits (ORION_E_ARG beyond them): nch <= 65535, num_syms <= 65535, num_tones <= 2^20,
- * nch * num_syms * num_tones < 2^31, max_cand <= 65536. */
+ * nch * num_syms * num_tones < 2^31, max_cand <= 65536.
+ *
+ * Streams and the digital handles (orion_sync, orion_ft_mod, the orion_psk31_*, orion_fft,
+ * orion_ofdm, orion_ofdm_acquire): a handle keeps two kinds of device memory.
+ * - Its tables (step phasors, windows, rotator phasors, twiddles, the OFDM grid and equalizer
+ *   coefficients) may be replaced by a call, a setter or a reset whatever streams the handle's
+ *   earlier calls used: replacing a table waits for the device first.
+ * - Its scratch (a sync's waterfall and score map, a search's run lists, staging) is shared
+ *   by its calls: calls that use it are ordered by the caller, on one stream or with events.
+ * The *_device entries are asynchronous on their stream except while a table is uploaded
+ * (a handle's first call and every replacement; a replacement waits for the whole device),
+ * while a buffer grows, or while the previous call's plan is still in use (the synthesisers
+ * and modulators, whose plan is built on the host: a call waits for the handle's previous
+ * launch). The entries that take host memory are synchronous and return with the result in
+ * place. The slot synthesisers without a
+ * handle (orion_ft_synth_*, orion_psk31_synth_*) share one plan per device: one call at a
+ * time, process-wide. */
 typedef struct orion_sync orion_sync;
 typedef struct {
   int32_t time_sym;  /* costas.rs:29-36 Candidate (freq_bin: usize there) */

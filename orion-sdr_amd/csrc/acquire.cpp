@@ -230,6 +230,15 @@ AcquireEngine::AcquireEngine(const acquire::Preamble& pre) : pre_(pre) {
   }
 }
 
+const f2* AcquireEngine::known(hipStream_t s) {
+  if (known_.empty()) {
+    std::vector<float> k(2 * pre_.tn_fft);
+    ofdm::training_pattern(pre_.tn_fft, k.data());
+    known_.set(k, s);
+  }
+  return known_.as<f2>();
+}
+
 void AcquireEngine::sync_batch(const void* iq, size_t ncap, size_t n, float fs, size_t start, size_t end_arg, float thr,
                                const SyncOut& o, hipStream_t s) {
   if (ncap == 0) return;
@@ -246,17 +255,12 @@ void AcquireEngine::sync_batch(const void* iq, size_t ncap, size_t n, float fs, 
                    static_cast<long long>(pre_.total_len()), o, s);
   if (!pre_.training) return;
   const size_t nf = pre_.tn_fft, cand = ncap * acquire::kTopN;
-  if (known_.size() == 0) {
-    std::vector<float> k(2 * nf);
-    ofdm::training_pattern(nf, k.data());
-    known_.upload(k.data(), k.size() * sizeof(float), s);
-  }
   sym_.resize(cand * nf * 8);
   freq_.resize(cand * nf * 8);
   launch_icfo_gather(x, nc, nn, static_cast<long long>(nd), static_cast<long long>(start), static_cast<int>(pre_.lead()),
                      static_cast<int>(nf), static_cast<int>(pre_.tcp), fs, o, sym_.as<f2>(), s);
   fft_->batch(sym_.as<void>(), nf, freq_.as<void>(), nf, cand, s);
-  launch_icfo_corr(freq_.as<f2>(), known_.as<f2>(), nc, nn, static_cast<int>(pre_.lead()), static_cast<int>(nf),
+  launch_icfo_corr(freq_.as<f2>(), known(s), nc, nn, static_cast<int>(pre_.lead()), static_cast<int>(nf),
                    static_cast<int>(pre_.tcp), o, s);
 }
 
@@ -276,14 +280,9 @@ void AcquireEngine::weights(const void* rows, size_t ncap, size_t n, size_t wind
   if (!pre_.training) throw std::invalid_argument("acquire: the preamble has no training symbol to estimate from");
   const size_t nf = pre_.tn_fft, at = pre_.lead() + window;
   if (window > pre_.tcp || at + nf > n) throw std::invalid_argument("acquire: the rows are shorter than the training symbol");
-  if (known_.size() == 0) {
-    std::vector<float> k(2 * nf);
-    ofdm::training_pattern(nf, k.data());
-    known_.upload(k.data(), k.size() * sizeof(float), s);
-  }
   freq_.resize(std::max(ncap * nf * 8, freq_.size()));
   fft_->batch(static_cast<const f2*>(rows) + at, n, freq_.as<void>(), nf, ncap, s);
-  launch_acq_weights(freq_.as<f2>(), known_.as<f2>(), static_cast<long long>(ncap * nf), static_cast<int>(nf),
+  launch_acq_weights(freq_.as<f2>(), known(s), static_cast<long long>(ncap * nf), static_cast<int>(nf),
                      static_cast<f2*>(w), s);
 }
 

@@ -133,7 +133,9 @@ class AcquireEngine {
  private:
   acquire::Preamble pre_;
   std::unique_ptr<FftDev> fft_;
-  DevBuf known_, sym_, freq_;
+  const f2* known(hipStream_t s);  // the training pattern on the device, uploaded by the first use
+  DevTable known_;
+  DevBuf sym_, freq_;
 };
 
 }  // namespace orion

@@ -40,11 +40,43 @@ void DevBuf::upload(const void* h, size_t bytes, hipStream_t s) {
   ORION_HIP(hipStreamSynchronize(s));
 }
 
-StagedIn::StagedIn(const void* src, size_t bytes, size_t slack) : buf_(bytes + slack), given_(src != nullptr) {
-  if (src && bytes) ORION_HIP(hipMemcpy(buf_.as<void>(), src, bytes, hipMemcpyHostToDevice));
+void DevTable::set(const void* h, size_t bytes, hipStream_t s) {
+  if (held_) ORION_HIP(hipDeviceSynchronize());
+  if (bytes) buf_.upload(h, bytes, s);
+  else buf_.resize(256);
+  held_ = true;
 }
-void stage_out(void* dst, const DevBuf& src, size_t bytes) {
-  if (dst && bytes) ORION_HIP(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost));
+
+PlanUpload::~PlanUpload() {
+  if (done_) (void)hipEventDestroy(done_);
+  if (pin_) (void)hipHostFree(pin_);
+}
+char* PlanUpload::begin(size_t bytes) {
+  if (!done_) ORION_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+  else ORION_HIP(hipEventSynchronize(done_));
+  if (bytes > pin_n_) {
+    if (pin_) ORION_HIP(hipHostFree(pin_));
+    pin_ = nullptr;
+    pin_n_ = 0;
+    ORION_HIP(hipHostMalloc(&pin_, bytes + bytes / 2, hipHostMallocDefault));
+    pin_n_ = bytes + bytes / 2;
+  }
+  dev_.resize(bytes);
+  bytes_ = bytes;
+  return static_cast<char*>(pin_);
+}
+const char* PlanUpload::push(hipStream_t s) {
+  ORION_HIP(hipMemcpyAsync(dev_.as<void>(), pin_, bytes_, hipMemcpyHostToDevice, s));
+  return dev_.as<char>();
+}
+void PlanUpload::done(hipStream_t s) { ORION_HIP(hipEventRecord(done_, s)); }
+
+void stage_in(DevBuf& dst, const void* src, size_t bytes, size_t slack) {
+  dst.resize(bytes + slack);
+  if (src && bytes) ORION_HIP(hipMemcpy(dst.as<void>(), src, bytes, hipMemcpyHostToDevice));
+}
+void stage_out(void* dst, const DevBuf& src, size_t bytes, size_t offset) {
+  if (dst && bytes) ORION_HIP(hipMemcpy(dst, src.as<char>() + offset, bytes, hipMemcpyDeviceToHost));
 }
 
 // ------------------------------------------------------------------- Block --

@@ -10,8 +10,11 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "design.hpp"
@@ -48,13 +51,75 @@ class DevBuf {
   size_t n_ = 0;
 };
 
-// The staging of a host-memory entry point: its inputs copied to the device (StagedIn), the
-// device entry on the null stream, its outputs copied back (stage_out), hipDeviceSynchronize.
-// A staged input is a device buffer of bytes + slack with the caller's bytes in it; nothing is
-// copied when the caller passed no pointer or no bytes.
+// A device copy of a host-built table that launches read. Replacing a table that already holds
+// contents synchronises the device first: launches of any stream may still be reading the old
+// one, and DevBuf::upload orders only the stream it copies on. So a handle's tables may change
+// whatever streams its earlier calls used; the first set() of a table waits for nothing.
+class DevTable {
+ public:
+  void set(const void* h, size_t bytes, hipStream_t s);
+  // An empty vector leaves a placeholder allocation, so that as() is a valid pointer.
+  template <class T> void set(const std::vector<T>& v, hipStream_t s) { set(v.data(), v.size() * sizeof(T), s); }
+  bool empty() const { return !held_; }  // never set
+  template <class T> T* as() const { return buf_.as<T>(); }
+
+ private:
+  DevBuf buf_;
+  bool held_ = false;
+};
+
+// A plan that the host builds for one call and one launch reads: pinned host space (copied by
+// DMA, no staging), its device copy, and an event that the next call waits on, so that the
+// copy and the launch are both asynchronous on the caller's stream. One call at a time.
+class PlanUpload {
+ public:
+  PlanUpload() = default;
+  ~PlanUpload();
+  PlanUpload(const PlanUpload&) = delete;
+  PlanUpload& operator=(const PlanUpload&) = delete;
+  // Waits for the previous call's copy and launch, then gives pinned space for bytes.
+  char* begin(size_t bytes);
+  // Queues the copy of those bytes on s; the device plan.
+  const char* push(hipStream_t s);
+  // After the launch that reads the device plan has been queued on s.
+  void done(hipStream_t s);
+
+ private:
+  DevBuf dev_;
+  void* pin_ = nullptr;
+  size_t pin_n_ = 0, bytes_ = 0;
+  hipEvent_t done_ = nullptr;  // the last copy out of pin_ and launch over dev_
+};
+
+// The home of what outlives every handle (a shared synthesiser, a code's tables): one T per
+// device (hipGetDevice) and key, made on first use, with init run on it before anyone else
+// sees it, and never destroyed, so that no HIP call runs at process exit. Each T has its own
+// home, so a T names one purpose.
+template <class T>
+T& per_device(int key = 0, void (*init)(T&, int key) = nullptr) {
+  static std::mutex mu;
+  static auto* const home = new std::map<std::pair<int, int>, T*>;
+  int dev = 0;
+  ORION_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  T*& slot = (*home)[{dev, key}];
+  if (!slot) {
+    std::unique_ptr<T> made(new T);
+    if (init) init(*made, key);
+    slot = made.release();
+  }
+  return *slot;
+}
+
+// The staging of a host-memory entry point: its inputs copied to the device (stage_in, or a
+// StagedIn where the buffer lives for the call), the device entry on the null stream, its
+// outputs copied back (stage_out), hipDeviceSynchronize.
+// stage_in grows dst to bytes + slack and copies the caller's bytes in; nothing is copied when
+// the caller passed no pointer or no bytes.
+void stage_in(DevBuf& dst, const void* src, size_t bytes, size_t slack = 16);
 class StagedIn {
  public:
-  StagedIn(const void* src, size_t bytes, size_t slack = 16);
+  StagedIn(const void* src, size_t bytes, size_t slack = 16) : given_(src != nullptr) { stage_in(buf_, src, bytes, slack); }
   template <class T> T* as() const { return buf_.as<T>(); }
   // null when the caller passed no pointer: an optional argument of the device entry
   template <class T> T* opt() const { return given_ ? buf_.as<T>() : nullptr; }
@@ -63,8 +128,8 @@ class StagedIn {
   DevBuf buf_;
   bool given_;
 };
-// Copies the first bytes of src to the caller's dst; a null or empty destination is skipped.
-void stage_out(void* dst, const DevBuf& src, size_t bytes);
+// Copies bytes of src, from offset on, to the caller's dst; a null or empty destination is skipped.
+void stage_out(void* dst, const DevBuf& src, size_t bytes, size_t offset = 0);
 
 class Block {
  public:

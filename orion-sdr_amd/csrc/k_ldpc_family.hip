@@ -25,9 +25,6 @@
 // reference's own (NaN and +-inf behave as on the host). Every loop over degrees is bounded
 // by a constant of the code.
 #include <algorithm>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <vector>
 
 #include "code_dev.hpp"
@@ -320,20 +317,12 @@ std::vector<uint32_t> make_table(const ldpcf::Ldpc& c) {
 }
 
 // the code's table on the current device: built and uploaded on first use, then kept
+struct CodeTable {
+  DevTable t;
+};
 const uint32_t* device_table(int code) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, std::unique_ptr<DevBuf>> tabs;
-  int dev = 0;
-  ORION_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  std::unique_ptr<DevBuf>& slot = tabs[{dev, code}];
-  if (!slot) {
-    const std::vector<uint32_t> t = make_table(ldpcf::Ldpc::get(code));
-    auto buf = std::make_unique<DevBuf>(t.size() * sizeof(uint32_t));
-    ORION_HIP(hipMemcpy(buf->as<void>(), t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    slot = std::move(buf);
-  }
-  return slot->as<uint32_t>();
+  return per_device<CodeTable>(code, [](CodeTable& c, int code) { c.t.set(make_table(ldpcf::Ldpc::get(code)), nullptr); })
+      .t.as<uint32_t>();
 }
 
 LdpcfGeom ldpcf_geom(size_t nstreams, size_t nblocks, size_t rows, size_t cols) {
@@ -374,12 +363,22 @@ size_t ldpcf_decode_blocks(int code, size_t n_llr, size_t rows, size_t cols) {
   return nblocks;
 }
 
-void ldpcf_decode_batch(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows, size_t cols,
-                        size_t max_iter, int rule, float scale, uint8_t* bits, int32_t* unsat, int32_t* iterations,
-                        hipStream_t s) {
+namespace {
+// The argument checks of the device entry, which the host entry runs before any device call: the
+// codewords per stream.
+size_t check_decode(int code, size_t nstreams, size_t n_llr, size_t rows, size_t cols, size_t max_iter, int rule) {
   const size_t nblocks = ldpcf_decode_blocks(code, n_llr, rows, cols);
   ldpcf::check_rule(rule);
   if (max_iter > kLdpcfMaxIter) throw std::invalid_argument("ldpc family decode: max_iter above 2^30");
+  ldpcf_geom(nstreams, nblocks, rows, cols);
+  return nblocks;
+}
+}  // namespace
+
+void ldpcf_decode_batch(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows, size_t cols,
+                        size_t max_iter, int rule, float scale, uint8_t* bits, int32_t* unsat, int32_t* iterations,
+                        hipStream_t s) {
+  const size_t nblocks = check_decode(code, nstreams, n_llr, rows, cols, max_iter, rule);
   LdpcfGeom g = ldpcf_geom(nstreams, nblocks, rows, cols);
   if (nstreams == 0) return;
   if (reinterpret_cast<uintptr_t>(llr) % 4 || reinterpret_cast<uintptr_t>(unsat) % 4 ||
@@ -403,10 +402,7 @@ void ldpcf_decode_batch(int code, const float* llr, size_t nstreams, size_t n_ll
 void ldpcf_decode_batch_host(int code, const float* llr, size_t nstreams, size_t n_llr, size_t rows, size_t cols,
                              size_t max_iter, int rule, float scale, uint8_t* bits, int32_t* unsat,
                              int32_t* iterations) {
-  const size_t nblocks = ldpcf_decode_blocks(code, n_llr, rows, cols);
-  ldpcf::check_rule(rule);
-  if (max_iter > kLdpcfMaxIter) throw std::invalid_argument("ldpc family decode: max_iter above 2^30");
-  ldpcf_geom(nstreams, nblocks, rows, cols);
+  const size_t nblocks = check_decode(code, nstreams, n_llr, rows, cols, max_iter, rule);
   if (nstreams == 0) return;
   const size_t lb = nstreams * n_llr * sizeof(float), bb = nstreams * nblocks * ldpcf::Ldpc::get(code).k(),
                sb = nstreams * nblocks * sizeof(int32_t);
@@ -429,18 +425,25 @@ size_t ldpcf_encoded_len(int code, size_t nbits, size_t rows, size_t cols) {
   return g.block ? (coded + g.block - 1) / g.block * g.block : coded;
 }
 
-void ldpcf_encode_batch(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows, size_t cols,
-                        uint8_t* coded, hipStream_t s) {
-  const size_t out_len = ldpcf_encoded_len(code, nbits, rows, cols);
-  const ldpcf::Ldpc& c = ldpcf::Ldpc::get(code);
-  const size_t nblocks = (nbits + c.k() - 1) / c.k();
-  LdpcfGeom g = ldpcf_geom(nstreams, nblocks, rows, cols);
-  if (nstreams == 0) return;
+namespace {
+// As check_decode, for an encode: its geometry.
+LdpcfGeom check_encode(int code, size_t nstreams, size_t nbits, size_t rows, size_t cols) {
+  const size_t out_len = ldpcf_encoded_len(code, nbits, rows, cols), k = ldpcf::Ldpc::get(code).k();
+  LdpcfGeom g = ldpcf_geom(nstreams, (nbits + k - 1) / k, rows, cols);
   g.stream_len = static_cast<uint32_t>(nbits);
   g.out_len = static_cast<uint32_t>(out_len);
+  return g;
+}
+}  // namespace
+
+void ldpcf_encode_batch(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows, size_t cols,
+                        uint8_t* coded, hipStream_t s) {
+  const LdpcfGeom g = check_encode(code, nstreams, nbits, rows, cols);
+  if (nstreams == 0) return;
+  const size_t nblocks = g.nblocks, out_len = g.out_len;
   const uint32_t* tab = device_table(code);
   // the last block's padding is written by nobody else
-  if (out_len != nblocks * c.n()) ORION_HIP(hipMemsetAsync(coded, 0, nstreams * out_len, s));
+  if (out_len != nblocks * ldpcf::Ldpc::get(code).n()) ORION_HIP(hipMemsetAsync(coded, 0, nstreams * out_len, s));
   const unsigned total = static_cast<unsigned>(nstreams * nblocks);
   if (code == ldpcf::kN512R12)
     k_ldpcf_encode<512, 256><<<total, 64, 0, s>>>(bits, g, tab, coded);
@@ -453,10 +456,9 @@ void ldpcf_encode_batch(int code, const uint8_t* bits, size_t nstreams, size_t n
 
 void ldpcf_encode_batch_host(int code, const uint8_t* bits, size_t nstreams, size_t nbits, size_t rows, size_t cols,
                              uint8_t* coded) {
-  const size_t out_len = ldpcf_encoded_len(code, nbits, rows, cols);
-  if (nstreams > kLdpcfMaxStreams) throw std::invalid_argument("ldpc family: nstreams above 2^24");
+  const LdpcfGeom g = check_encode(code, nstreams, nbits, rows, cols);
   if (nstreams == 0) return;
-  const size_t ib = nstreams * nbits, ob = nstreams * out_len;
+  const size_t ib = nstreams * nbits, ob = nstreams * g.out_len;
   StagedIn d_in(bits, ib);
   DevBuf d_out(ob + 16);
   ldpcf_encode_batch(code, d_in.as<uint8_t>(), nstreams, nbits, rows, cols, d_out.as<uint8_t>(), nullptr);

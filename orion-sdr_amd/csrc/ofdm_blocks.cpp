@@ -14,13 +14,6 @@ int log2_of(size_t n) {
   while ((size_t{1} << b) < n) ++b;
   return b;
 }
-template <class T>
-void put(DevBuf& b, const std::vector<T>& v, hipStream_t s) {
-  if (v.empty())
-    b.resize(256);
-  else
-    b.upload(v.data(), v.size() * sizeof(T), s);
-}
 void check_ptr8(const void* p) {
   if (reinterpret_cast<uintptr_t>(p) % 8) throw std::invalid_argument("ofdm: cf32 buffer not 8-byte aligned");
 }
@@ -35,7 +28,7 @@ void FftDev::batch(const void* in, size_t in_stride, void* out, size_t out_strid
   if (batch > kMaxSymbols) throw std::invalid_argument("fft: more than 2^30 symbols in one call");
   check_ptr8(in);
   check_ptr8(out);
-  if (tw_.size() == 0) tw_.upload(host_.twiddles().data(), host_.twiddles().size() * sizeof(float), s);
+  if (tw_.empty()) tw_.set(host_.twiddles(), s);
   launch_fft(static_cast<const f2*>(in), static_cast<long long>(in_stride), static_cast<f2*>(out),
              static_cast<long long>(out_stride), static_cast<long long>(batch), static_cast<int>(n), log2_of(n),
              tw_.as<f2>(), host_.inverse(), s);
@@ -44,10 +37,10 @@ void FftDev::batch(const void* in, size_t in_stride, void* out, size_t out_strid
 WorkReport FftDev::process_host(const void* in, size_t n_in, void* out, size_t out_cap) {
   const size_t n = host_.n();
   if (n_in < n || out_cap < n) return {};
-  h_in_.upload(in, n * 8, nullptr);
+  stage_in(h_in_, in, n * 8, 0);
   h_out_.resize(n * 8);
   batch(h_in_.as<void>(), n, h_out_.as<void>(), n, 1, nullptr);
-  ORION_HIP(hipMemcpy(out, h_out_.as<void>(), n * 8, hipMemcpyDeviceToHost));
+  stage_out(out, h_out_, n * 8);
   ORION_HIP(hipDeviceSynchronize());
   return {n, n};
 }
@@ -67,7 +60,6 @@ const OfdmDev& OfdmEngine::dev(hipStream_t s) {
   const ofdm::Grid& g = mod_.grid();
   const size_t n = c.plan.n_fft;
   if (!up_) {
-    if (tw_.size()) ORION_HIP(hipDeviceSynchronize());  // launches in flight read the tables that are replaced
     const ofdm::Equalizer identity(c, ofdm::kEqTrainingSymbolHold);
     const ofdm::Equalizer& e = eq_ ? *eq_ : identity;
     std::vector<int32_t> map(n, -1), emap(n, 0);
@@ -81,18 +73,18 @@ const OfdmDev& OfdmEngine::dev(hipStream_t s) {
       ofdm::axis_table(bps, axis.data());
       ofdm::threshold_table(bps, thr.data());
     }
-    put(tw_, mod_.ifft().twiddles(), s);
-    put(map_, map, s);
-    put(pval_, g.pilot_val, s);
-    put(dbin_, g.data_bins, s);
-    put(spbin_, e.pilot_bins(), s);
-    put(spval_, e.pilot_val(), s);
-    put(emap_, emap, s);
-    put(weight_, e.weight(), s);
-    put(hold_, e.estimate(), s);
-    put(ramp_, mod_.ramp(), s);
-    put(axis_, axis, s);
-    put(thr_, thr, s);
+    tw_.set(mod_.ifft().twiddles(), s);
+    map_.set(map, s);
+    pval_.set(g.pilot_val, s);
+    dbin_.set(g.data_bins, s);
+    spbin_.set(e.pilot_bins(), s);
+    spval_.set(e.pilot_val(), s);
+    emap_.set(emap, s);
+    weight_.set(e.weight(), s);
+    hold_.set(e.estimate(), s);
+    ramp_.set(mod_.ramp(), s);
+    axis_.set(axis, s);
+    thr_.set(thr, s);
     d_.n = static_cast<int>(n);
     d_.log2n = log2_of(n);
     d_.cp = static_cast<int>(c.plan.cp_len);
@@ -118,8 +110,7 @@ const OfdmDev& OfdmEngine::dev(hipStream_t s) {
     weight_dirty_ = false;
   }
   if (weight_dirty_ && eq_) {
-    ORION_HIP(hipDeviceSynchronize());  // launches in flight read the coefficients that are replaced
-    weight_.upload(eq_->weight().data(), eq_->weight().size() * sizeof(float), s);
+    weight_.set(eq_->weight(), s);
     weight_dirty_ = false;
   }
   return d_;
@@ -216,21 +207,15 @@ void OfdmEngine::equalize(const void* in, size_t nsym, void* out, hipStream_t s)
 }
 
 // ---- host memory --------------------------------------------------------------------------
-namespace {
-void download(void* dst, const DevBuf& src, size_t bytes) {
-  ORION_HIP(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost));
-  ORION_HIP(hipDeviceSynchronize());
-}
-}  // namespace
-
 WorkReport OfdmEngine::mod_host(const uint8_t* bits, size_t n_bits, void* iq, size_t out_cap) {
   const size_t bps = config().bits_per_ofdm_symbol(), len = config().samples_per_ofdm_symbol();
   const size_t k = std::min(n_bits / bps, out_cap / len);
   if (k == 0) return {};
-  h_in_.upload(bits, k * bps, nullptr);
+  stage_in(h_in_, bits, k * bps, 0);
   h_out_.resize(k * len * 8);
   modulate(h_in_.as<uint8_t>(), 1, k, h_out_.as<void>(), nullptr);
-  download(iq, h_out_, k * len * 8);
+  stage_out(iq, h_out_, k * len * 8);
+  ORION_HIP(hipDeviceSynchronize());
   return {k * bps, k * len};
 }
 
@@ -238,10 +223,11 @@ WorkReport OfdmEngine::demod_host(const void* iq, size_t n, void* soft, size_t o
   const size_t len = config().samples_per_ofdm_symbol(), nd = num_data();
   const size_t k = std::min(n / len, out_cap / nd);
   if (k == 0) return {};
-  h_in_.upload(iq, k * len * 8, nullptr);
+  stage_in(h_in_, iq, k * len * 8, 0);
   h_out_.resize(k * nd * 8);
   demodulate(h_in_.as<void>(), 1, k, h_out_.as<void>(), nullptr, nullptr, nullptr);
-  download(soft, h_out_, k * nd * 8);
+  stage_out(soft, h_out_, k * nd * 8);
+  ORION_HIP(hipDeviceSynchronize());
   return {k * len, k * nd};
 }
 
@@ -249,10 +235,11 @@ WorkReport OfdmEngine::decide_host(const void* soft, size_t n, uint8_t* bits, si
   const size_t nd = num_data(), bps = config().bits_per_ofdm_symbol();
   const size_t k = std::min(n / nd, out_cap / bps);
   if (k == 0) return {};
-  h_in_.upload(soft, k * nd * 8, nullptr);
+  stage_in(h_in_, soft, k * nd * 8, 0);
   h_out_.resize(k * bps);
   decide(h_in_.as<void>(), k * nd, h_out_.as<uint8_t>(), nullptr);
-  download(bits, h_out_, k * bps);
+  stage_out(bits, h_out_, k * bps);
+  ORION_HIP(hipDeviceSynchronize());
   return {k * nd, k * bps};
 }
 
@@ -260,10 +247,11 @@ WorkReport OfdmEngine::soft_demod_host(const void* soft, size_t n, float* llr, s
   const size_t nd = num_data(), bps = config().bits_per_ofdm_symbol();
   const size_t k = std::min(n / nd, out_cap / bps);
   if (k == 0) return {};
-  h_in_.upload(soft, k * nd * 8, nullptr);
+  stage_in(h_in_, soft, k * nd * 8, 0);
   h_out_.resize(k * bps * 4);
   soft_demod(h_in_.as<void>(), k * nd, h_out_.as<float>(), nullptr);
-  download(llr, h_out_, k * bps * 4);
+  stage_out(llr, h_out_, k * bps * 4);
+  ORION_HIP(hipDeviceSynchronize());
   return {k * nd, k * bps};
 }
 
@@ -271,10 +259,11 @@ WorkReport OfdmEngine::equalize_host(const void* in, size_t n, void* out, size_t
   const size_t nf = config().plan.n_fft;
   const size_t k = std::min(n / nf, out_cap / nf);
   if (k == 0) return {};
-  h_in_.upload(in, k * nf * 8, nullptr);
+  stage_in(h_in_, in, k * nf * 8, 0);
   h_out_.resize(k * nf * 8);
   equalize(h_in_.as<void>(), k, h_out_.as<void>(), nullptr);
-  download(out, h_out_, k * nf * 8);
+  stage_out(out, h_out_, k * nf * 8);
+  ORION_HIP(hipDeviceSynchronize());
   return {k * nf, k * nf};
 }
 

@@ -68,7 +68,8 @@ class FftDev {
 
  private:
   ofdm::Fft host_;
-  DevBuf tw_, h_in_, h_out_;
+  DevTable tw_;
+  DevBuf h_in_, h_out_;
 };
 
 // One OfdmConfig on the device. Constructing it touches no device; the tables are uploaded
@@ -126,7 +127,7 @@ class OfdmEngine {
   std::unique_ptr<RefOsc> osc_;
   OfdmDev d_{};
   bool up_ = false, weight_dirty_ = false;
-  DevBuf tw_, map_, pval_, dbin_, spbin_, spval_, emap_, weight_, hold_, ramp_, axis_, thr_;
+  DevTable tw_, map_, pval_, dbin_, spbin_, spval_, emap_, weight_, hold_, ramp_, axis_, thr_;
   DevBuf h_in_, h_out_;
 };
 

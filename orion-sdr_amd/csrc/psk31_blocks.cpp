@@ -2,6 +2,7 @@
 #include "psk31_blocks.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <mutex>
 #include <stdexcept>
 #include <vector>
@@ -93,7 +94,6 @@ void Psk31DemodBank::set_gain(size_t slot, float gain) {
 }
 
 void Psk31DemodBank::reset() {
-  if (d_st_.size()) ORION_HIP(hipDeviceSynchronize());  // launches in flight still carry the old states
   base_ = 0;
   fresh_ = true;
 }
@@ -107,18 +107,10 @@ void Psk31DemodBank::process(const void* iq, size_t nch, size_t n, float* soft, 
   const auto misaligned = [](const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
   if (misaligned(iq, 8) || misaligned(reports, 8) || misaligned(soft, 4))
     throw std::invalid_argument("psk31 bank: iq / reports not 8-byte aligned, or soft not 4-byte aligned");
-  if (fresh_) {
-    d_rec_.upload(rec_.data(), rec_.size() * sizeof(psk31::BankRecord), s);
-    d_st_.upload(st0_.data(), st0_.size() * sizeof(psk31::DemodState), s);
-    d_hann_.upload(hann_.data(), hann_.size() * sizeof(float), s);
-    fresh_ = false;
-    rec_dirty_ = false;
-  }
-  if (rec_dirty_) {
-    ORION_HIP(hipDeviceSynchronize());  // launches in flight read the old records
-    d_rec_.upload(rec_.data(), rec_.size() * sizeof(psk31::BankRecord), s);
-    rec_dirty_ = false;
-  }
+  if (fresh_) d_st_.set(st0_, s);  // after a reset this waits for the launches that carry the old states
+  if (fresh_ || rec_dirty_) d_rec_.set(rec_, s);
+  if (d_hann_.empty()) d_hann_.set(hann_, s);
+  fresh_ = rec_dirty_ = false;
   launch_psk31_demod(static_cast<const f2*>(iq), static_cast<long long>(n), base_, d_rec_.as<psk31::BankRecord>(),
                      d_st_.as<psk31::DemodState>(), static_cast<int>(rec_.size()), d_hann_.as<float>(),
                      static_cast<uint32_t>(sps_), soft, static_cast<long long>(out_stride), bits,
@@ -132,18 +124,17 @@ void Psk31DemodBank::process_host(const void* iq, size_t nch, size_t n, float* s
   if (out_stride < max_cap_) throw std::invalid_argument("psk31 bank: out_stride below the largest out_cap");
   const size_t ns = rec_.size(), ib = nch * n * 8, sb = ns * out_stride * sizeof(float), bb = bits ? ns * out_stride : 0;
   const size_t rb = ns * 2 * sizeof(uint64_t);
-  h_iq_.resize(ib + 16);
+  stage_in(h_iq_, iq, ib);
   h_soft_.resize(sb + 16);
   h_bits_.resize(bb + 16);
   h_rep_.resize(rb);
-  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
   if (sb) ORION_HIP(hipMemset(h_soft_.as<void>(), 0, sb));
   if (bb) ORION_HIP(hipMemset(h_bits_.as<void>(), 0, bb));
   process(h_iq_.as<void>(), nch, n, h_soft_.as<float>(), out_stride, bits ? h_bits_.as<uint8_t>() : nullptr,
           h_rep_.as<uint64_t>(), nullptr);
-  if (sb) ORION_HIP(hipMemcpy(soft, h_soft_.as<void>(), sb, hipMemcpyDeviceToHost));
-  if (bb) ORION_HIP(hipMemcpy(bits, h_bits_.as<void>(), bb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(reports, h_rep_.as<void>(), rb, hipMemcpyDeviceToHost));
+  stage_out(soft, h_soft_, sb);
+  stage_out(bits, h_bits_, bb);
+  stage_out(reports, h_rep_, rb);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -153,19 +144,18 @@ void Psk31ModDev::run(const std::vector<float>& ph, size_t nstreams, size_t n, v
   if (nstreams > 0x7fffffffull || per > (1ull << 40)) throw std::invalid_argument("psk31 mod: batch too large");
   if (reinterpret_cast<uintptr_t>(iq_dev) % 8) throw std::invalid_argument("psk31 mod: iq not 8-byte aligned");
   if (nstreams == 0 || n == 0) return;
-  if (hann_.size() == 0) hann_.upload(host_.hann().data(), sps * sizeof(float), s);
+  if (hann_.empty()) hann_.set(host_.hann().data(), sps * sizeof(float), s);
   if (host_.rf_hz() != 0.0f && rot_n_ < per) {  // a fresh Rotator per call: any call's phasors are a prefix
-    ORION_HIP(hipDeviceSynchronize());          // launches in flight read the table that is replaced
     std::vector<float> z(2 * per);
     psk31::rotator_table(host_.rf_hz(), host_.fs(), per, z.data());
-    rot_.upload(z.data(), z.size() * sizeof(float), s);
+    rot_.set(z, s);
     rot_n_ = per;
   }
-  ph_.upload(ph.data(), ph.size() * sizeof(float), s);
-  launch_psk31_mod(ph_.as<f2>(), hann_.as<float>(), host_.rf_hz() != 0.0f ? rot_.as<f2>() : nullptr,
-                   static_cast<int>(nstreams), static_cast<long long>(n), static_cast<uint32_t>(sps), host_.gain(),
-                   static_cast<f2*>(iq_dev), s);
-  ORION_HIP(hipStreamSynchronize(s));  // ph_ is rewritten by the next call
+  std::memcpy(ph_.begin(ph.size() * sizeof(float)), ph.data(), ph.size() * sizeof(float));
+  launch_psk31_mod(reinterpret_cast<const f2*>(ph_.push(s)), hann_.as<float>(),
+                   host_.rf_hz() != 0.0f ? rot_.as<f2>() : nullptr, static_cast<int>(nstreams),
+                   static_cast<long long>(n), static_cast<uint32_t>(sps), host_.gain(), static_cast<f2*>(iq_dev), s);
+  ph_.done(s);
 }
 
 void Psk31ModDev::modulate(const uint8_t* bits, size_t n, void* iq_dev, hipStream_t s) {
@@ -189,16 +179,23 @@ void Psk31ModDev::modulate_batch_host(const uint8_t* bits, size_t nstreams, size
   if (ob == 0) return;
   h_out_.resize(ob);
   modulate_batch(bits, nstreams, n, h_out_.as<void>(), nullptr);
-  ORION_HIP(hipMemcpy(iq, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(iq, h_out_, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
 // ---- band synthesis ----
+namespace {
+std::mutex g_synth_mu;
+struct Psk31SynthDev {  // one per device (blocks.hpp per_device)
+  PlanUpload plan;  // records | rows | phasors, each at a 16-byte offset
+  DevTable hann;    // the window for hann_fs
+  float hann_fs = 0.0f;
+};
+size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+}  // namespace
+
 void psk31_synth(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
                  bool accumulate, void* iq_dev, hipStream_t s) {
-  static std::mutex mu;
-  static DevBuf d_rec, d_rows, d_ph, d_hann;
-  static float hann_fs = 0.0f;
   if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("psk31 synth: 1 <= nch <= 65535");
   if (nsig > (1u << 24) || n > (1ull << 40)) throw std::invalid_argument("psk31 synth: nsig <= 2^24, n <= 2^40");
   if (reinterpret_cast<uintptr_t>(iq_dev) % 8) throw std::invalid_argument("psk31 synth: iq not 8-byte aligned");
@@ -217,7 +214,7 @@ void psk31_synth(float fs, const psk31::Signal* signals, const uint8_t* bits, si
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return signals[a].channel < signals[b].channel; });
   std::vector<psk31::SynthRecord> rec(nsig);
   std::vector<uint32_t> rows(nch + 1, 0);
-  std::vector<float> ph(2 * (total_bits + nsig) + 2);
+  std::vector<float> ph(2 * (total_bits + nsig));
   size_t at = 0;
   for (size_t j = 0; j < nsig; ++j) {
     const psk31::Signal& g = signals[order[j]];
@@ -231,28 +228,32 @@ void psk31_synth(float fs, const psk31::Signal* signals, const uint8_t* bits, si
     rows[g.channel + 1] += 1;
   }
   for (size_t ch = 0; ch < nch; ++ch) rows[ch + 1] += rows[ch];
-  std::lock_guard<std::mutex> lock(mu);
-  ORION_HIP(hipDeviceSynchronize());  // an earlier launch may still read the plan that is replaced
-  if (hann_fs != fs || d_hann.size() == 0) {
-    d_hann.upload(proto.hann().data(), sps * sizeof(float), s);
-    hann_fs = fs;
+  const size_t rec_b = nsig * sizeof(psk31::SynthRecord), rows_b = rows.size() * sizeof(uint32_t);
+  const size_t rows_at = up16(rec_b), ph_at = rows_at + up16(rows_b);
+  std::lock_guard<std::mutex> lock(g_synth_mu);
+  Psk31SynthDev& d = per_device<Psk31SynthDev>();
+  char* h = d.plan.begin(ph_at + ph.size() * sizeof(float));
+  if (rec_b) std::memcpy(h, rec.data(), rec_b);
+  std::memcpy(h + rows_at, rows.data(), rows_b);
+  if (!ph.empty()) std::memcpy(h + ph_at, ph.data(), ph.size() * sizeof(float));
+  if (d.hann_fs != fs || d.hann.empty()) {
+    d.hann.set(proto.hann().data(), sps * sizeof(float), s);
+    d.hann_fs = fs;
   }
-  rec.resize(nsig + 1);  // never an empty upload
-  d_rec.upload(rec.data(), rec.size() * sizeof(psk31::SynthRecord), s);
-  d_rows.upload(rows.data(), rows.size() * sizeof(uint32_t), s);
-  d_ph.upload(ph.data(), ph.size() * sizeof(float), s);
-  launch_psk31_synth(d_rec.as<psk31::SynthRecord>(), d_rows.as<uint32_t>(), d_ph.as<f2>(), d_hann.as<float>(),
-                     static_cast<uint32_t>(sps), static_cast<int>(nch), static_cast<long long>(n), accumulate,
-                     static_cast<f2*>(iq_dev), s);
+  const char* dev = d.plan.push(s);
+  launch_psk31_synth(reinterpret_cast<const psk31::SynthRecord*>(dev), reinterpret_cast<const uint32_t*>(dev + rows_at),
+                     reinterpret_cast<const f2*>(dev + ph_at), d.hann.as<float>(), static_cast<uint32_t>(sps),
+                     static_cast<int>(nch), static_cast<long long>(n), accumulate, static_cast<f2*>(iq_dev), s);
+  d.plan.done(s);
 }
 
 void psk31_synth_host(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
                       bool accumulate, void* iq) {
   const size_t ob = nch * n * 8;
-  DevBuf d_out(ob + 16);
-  if (ob && accumulate) ORION_HIP(hipMemcpy(d_out.as<void>(), iq, ob, hipMemcpyHostToDevice));
+  DevBuf d_out;
+  stage_in(d_out, accumulate ? iq : nullptr, ob);
   psk31_synth(fs, signals, bits, nsig, nch, n, accumulate, d_out.as<void>(), nullptr);
-  if (ob) ORION_HIP(hipMemcpy(iq, d_out.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(iq, d_out, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -267,6 +268,13 @@ void check_search(size_t nch, size_t num_syms, size_t num_bins, size_t max_cand)
     throw std::invalid_argument("psk31 sync: waterfall above 2^31 - 1 cells");
   if (nch * num_bins * max_cand > (1ull << 26) || num_bins * max_cand > (1ull << 22))
     throw std::invalid_argument("psk31 sync: nch * num_bins * max_cand <= 2^26 and num_bins * max_cand <= 2^22");
+}
+// The stride of sync's per-slot outputs, once nch, max_cand and n_bits are in range. The host
+// entry sizes its staging from it, so there it runs before any device call.
+size_t check_stride(size_t slots, size_t n_bits) {
+  if (slots * (n_bits + 2) > (1ull << 32))
+    throw std::invalid_argument("psk31 sync: nch * max_cand * (n_bits + 2) above 2^32");
+  return n_bits + 2;
 }
 }  // namespace
 
@@ -297,8 +305,7 @@ void Psk31Sync::sync(Sync& eng, const void* iq, size_t nch, size_t n, float fs, 
   const size_t sps = psk31::psk31_sps(fs);
   const size_t num_syms = sps ? n / sps : 0;
   check_search(nch, num_syms, num_bins, max_cand);
-  const size_t slots = nch * max_cand, stride = n_bits + 2;
-  if (slots * stride > (1ull << 32)) throw std::invalid_argument("psk31 sync: nch * max_cand * (n_bits + 2) above 2^32");
+  const size_t slots = nch * max_cand, stride = check_stride(slots, n_bits);
   ORION_HIP(hipMemsetAsync(soft, 0, slots * stride * sizeof(float), s));
   ORION_HIP(hipMemsetAsync(reports, 0, slots * 2 * sizeof(uint64_t), s));
   if (num_syms == 0) {  // psk31_sync.rs:60-68: no candidates
@@ -306,9 +313,9 @@ void Psk31Sync::sync(Sync& eng, const void* iq, size_t nch, size_t n, float fs, 
     ORION_HIP(hipMemsetAsync(count, 0, nch * sizeof(uint32_t), s));
     return;
   }
-  if (fs != hann_fs_ || hann_.size() == 0) {
+  if (fs != hann_fs_ || hann_.empty()) {
     const psk31::Demod proto(psk31::kBpsk, fs, 0.0f, 1.0f, 0);
-    hann_.upload(proto.hann().data(), proto.hann().size() * sizeof(float), s);
+    hann_.set(proto.hann(), s);
     hann_sq_sum_ = proto.hann_sq_sum();
     hann_fs_ = fs;
     st_bins_ = 0;
@@ -323,7 +330,7 @@ void Psk31Sync::sync(Sync& eng, const void* iq, size_t nch, size_t n, float fs, 
       w[3 * b + 2] = carrier != 0.0f ? 1.0f : 0.0f;
       if (carrier != 0.0f) psk31::rotator_step(-carrier, fs, &w[3 * b], &w[3 * b + 1]);
     }
-    steps_.upload(w.data(), w.size() * sizeof(float), s);
+    steps_.set(w, s);
     st_bins_ = num_bins;
     st_fs_ = fs;
     st_base_ = base_hz;
@@ -345,15 +352,13 @@ void Psk31Sync::find_carriers_host(const float* wf, size_t nch, size_t num_syms,
                                    size_t min_carrier_syms, float peak_margin_db, size_t max_cand, SyncCandidate* cand,
                                    uint32_t* count) {
   check_search(nch, num_syms, num_bins, max_cand);
-  const size_t wb = nch * num_syms * num_bins * sizeof(float), cb = nch * max_cand * sizeof(SyncCandidate);
-  h_in_.resize(wb + 16);
-  h_cand_.resize(cb);
-  h_count_.resize(nch * sizeof(uint32_t));
-  if (wb) ORION_HIP(hipMemcpy(h_in_.as<void>(), wf, wb, hipMemcpyHostToDevice));
+  const size_t nb = nch * sizeof(uint32_t), n_off = cand_count_offset(nch, max_cand);
+  stage_in(h_in_, wf, nch * num_syms * num_bins * sizeof(float));
+  h_cand_.resize(n_off + nb + 16);
   find_carriers(h_in_.as<float>(), nch, num_syms, num_bins, min_carrier_syms, peak_margin_db, max_cand,
-                h_cand_.as<SyncCandidate>(), h_count_.as<uint32_t>(), nullptr);
-  ORION_HIP(hipMemcpy(cand, h_cand_.as<void>(), cb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(count, h_count_.as<void>(), nch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                h_cand_.as<SyncCandidate>(), reinterpret_cast<uint32_t*>(h_cand_.as<char>() + n_off), nullptr);
+  stage_out(cand, h_cand_, nch * max_cand * sizeof(SyncCandidate));
+  stage_out(count, h_cand_, nb, n_off);
   ORION_HIP(hipDeviceSynchronize());
 }
 
@@ -363,22 +368,20 @@ void Psk31Sync::sync_host(Sync& eng, const void* iq, size_t nch, size_t n, float
   if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
   if (max_cand > kMaxCand || nch < 1 || nch > kMaxCh || n_bits > (1u << 30) - 2)
     throw std::invalid_argument("psk31 sync: 1 <= nch <= 65535, max_cand <= 65536, n_bits <= 2^30 - 2");
-  const size_t slots = nch * max_cand, stride = n_bits + 2;
-  if (slots * stride > (1ull << 32)) throw std::invalid_argument("psk31 sync: nch * max_cand * (n_bits + 2) above 2^32");
-  const size_t ib = nch * n * 8, cb = slots * sizeof(SyncCandidate), sb = slots * stride * sizeof(float);
-  const size_t rb = slots * 2 * sizeof(uint64_t);
-  h_in_.resize(ib + 16);
-  h_cand_.resize(cb);
-  h_count_.resize(nch * sizeof(uint32_t));
+  const size_t slots = nch * max_cand, stride = check_stride(slots, n_bits);
+  const size_t sb = slots * stride * sizeof(float), rb = slots * 2 * sizeof(uint64_t);
+  const size_t nb = nch * sizeof(uint32_t), n_off = cand_count_offset(nch, max_cand);
+  stage_in(h_in_, iq, nch * n * 8);
+  h_cand_.resize(n_off + nb + 16);
   h_soft_.resize(sb);
   h_rep_.resize(rb);
-  if (ib) ORION_HIP(hipMemcpy(h_in_.as<void>(), iq, ib, hipMemcpyHostToDevice));
   sync(eng, h_in_.as<void>(), nch, n, fs, base_hz, max_hz, min_carrier_syms, peak_margin_db, n_bits, max_cand,
-       h_cand_.as<SyncCandidate>(), h_count_.as<uint32_t>(), h_soft_.as<float>(), h_rep_.as<uint64_t>(), nullptr);
-  ORION_HIP(hipMemcpy(cand, h_cand_.as<void>(), cb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(count, h_count_.as<void>(), nch * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(soft, h_soft_.as<void>(), sb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(reports, h_rep_.as<void>(), rb, hipMemcpyDeviceToHost));
+       h_cand_.as<SyncCandidate>(), reinterpret_cast<uint32_t*>(h_cand_.as<char>() + n_off), h_soft_.as<float>(),
+       h_rep_.as<uint64_t>(), nullptr);
+  stage_out(cand, h_cand_, slots * sizeof(SyncCandidate));
+  stage_out(count, h_cand_, nb, n_off);
+  stage_out(soft, h_soft_, sb);
+  stage_out(reports, h_rep_, rb);
   ORION_HIP(hipDeviceSynchronize());
 }
 

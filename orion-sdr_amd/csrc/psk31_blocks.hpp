@@ -51,7 +51,8 @@ class Psk31DemodBank {
   std::vector<psk31::BankRecord> rec_;
   std::vector<psk31::DemodState> st0_;
   std::vector<float> hann_;
-  DevBuf d_rec_, d_st_, d_hann_, h_iq_, h_soft_, h_bits_, h_rep_;
+  DevTable d_rec_, d_st_, d_hann_;
+  DevBuf h_iq_, h_soft_, h_bits_, h_rep_;
 };
 
 // Bpsk31Mod / Qpsk31Mod with a device path (k_psk31_mod). host() is the scalar modulator
@@ -63,7 +64,8 @@ class Psk31ModDev {
   Psk31ModDev(int mode, float fs, float rf_hz, float gain) : host_(mode, fs, rf_hz, gain) {}
   psk31::Mod& host() { return host_; }
   // One stream from the modulator's current state, which advances as modulate_bits' does:
-  // bits [n] (host) -> iq [n * sps] cf32 (device), asynchronous on s after the upload.
+  // bits [n] (host) -> iq [n * sps] cf32 (device), asynchronous on s: a call waits only for
+  // the handle's previous launch (blocks.hpp PlanUpload).
   void modulate(const uint8_t* bits, size_t n, void* iq_dev, hipStream_t s);
   // nstreams independent streams, each from a fresh modulator of these parameters (the
   // state is not touched): bits [nstreams][n] (host) -> iq [nstreams][n * sps] (device).
@@ -74,15 +76,17 @@ class Psk31ModDev {
  private:
   void run(const std::vector<float>& ph, size_t nstreams, size_t n, void* iq_dev, hipStream_t s);
   psk31::Mod host_;
-  DevBuf ph_, hann_, rot_, h_out_;
+  PlanUpload ph_;  // a call's symbol phasors
+  DevTable hann_, rot_;
+  DevBuf h_out_;
   size_t rot_n_ = 0;
 };
 
 // Band synthesis (k_psk31_synth): signals [nsig] and their bits concatenated (host memory) ->
 // iq [nch][n] cf32 on the device. The plan (records sorted by channel, symbol phasors from
-// fresh modulators) is built on the host and uploaded; the launch is queued on s. One call
-// at a time, process-wide. Throws std::invalid_argument for a channel >= nch, an unknown
-// mode, or sizes above the limits.
+// fresh modulators) is built on the host; its copy and the launch are queued on s (blocks.hpp
+// PlanUpload, one per device). One call at a time, process-wide. Throws
+// std::invalid_argument for a channel >= nch, an unknown mode, or sizes above the limits.
 void psk31_synth(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
                  bool accumulate, void* iq_dev, hipStream_t s);
 void psk31_synth_host(float fs, const psk31::Signal* signals, const uint8_t* bits, size_t nsig, size_t nch, size_t n,
@@ -114,8 +118,9 @@ class Psk31Sync {
                  uint32_t* count, float* soft, uint64_t* reports);
 
  private:
-  DevBuf wf_, med_, floor_, runs_, nruns_, head_, rec_, st_, hann_, steps_;
-  DevBuf h_in_, h_cand_, h_count_, h_soft_, h_rep_;
+  DevBuf wf_, med_, floor_, runs_, nruns_, head_, rec_, st_;
+  DevTable hann_, steps_;
+  DevBuf h_in_, h_cand_, h_soft_, h_rep_;
   float st_fs_ = 0, st_base_ = 0, hann_fs_ = 0, hann_sq_sum_ = 1.0f;
   size_t st_bins_ = 0;
 };

@@ -34,6 +34,13 @@ void check_grid(size_t nch, size_t num_syms, size_t num_tones) {
   if (num_syms > kMaxSyms || num_tones > kMaxTones) throw std::invalid_argument("sync: num_syms <= 65535, num_tones <= 2^20");
   if (nch * num_syms * num_tones > 0x7fffffffull) throw std::invalid_argument("sync: waterfall above 2^31 - 1 cells");
 }
+// What a search is sized from; the host entries check it before any device call.
+void check_slots(size_t nch, size_t max_cand) {
+  // costas.rs:159: the reference reads heap[0] of an empty Vec when max_candidates == 0
+  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
+  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
+}
 }  // namespace
 
 std::vector<float> waterfall_steps(float fs, float base_hz, float tone_spacing_hz, size_t num_tones) {
@@ -91,9 +98,8 @@ void Sync::waterfall(const void* iq, float fs, float base_hz, float tone_spacing
   if (n_per_ch > (1ull << 40) || time_offset > (1ull << 40)) throw std::invalid_argument("waterfall: length above 2^40");
   if (num_syms == 0 || num_tones == 0) return;
   if (num_tones != st_tones_ || fs != st_fs_ || base_hz != st_base_ || tone_spacing_hz != st_spacing_ ||
-      steps_.size() == 0) {
-    const std::vector<float> w = waterfall_steps(fs, base_hz, tone_spacing_hz, num_tones);
-    steps_.upload(w.data(), w.size() * sizeof(float), s);
+      steps_.empty()) {
+    steps_.set(waterfall_steps(fs, base_hz, tone_spacing_hz, num_tones), s);
     st_tones_ = num_tones;
     st_fs_ = fs;
     st_base_ = base_hz;
@@ -108,9 +114,7 @@ void Sync::waterfall(const void* iq, float fs, float base_hz, float tone_spacing
 void Sync::find_candidates(const float* wf, size_t nch, size_t num_syms, size_t num_tones, int pattern, int t_min,
                            int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, hipStream_t s) {
   const Mode& m = mode_of(pattern);
-  // costas.rs:159: the reference reads heap[0] of an empty Vec when max_candidates == 0
-  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
-  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
+  check_slots(nch, max_cand);
   check_grid(nch, num_syms, num_tones);
   size_t cells = 0;
   if (num_tones > static_cast<size_t>(m.tones) && t_max >= t_min) {
@@ -191,34 +195,35 @@ void Sync::decode(int pattern, const void* iq, size_t nch, size_t n_per_ch, floa
 void Sync::decode_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
                        int t_min, int t_max, size_t max_cand, int rule, size_t max_iter, SyncCandidate* cand,
                        uint32_t* count, float* llr, void* results, DecodePick* pick) {
-  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
-  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
-  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
+  check_slots(nch, max_cand);
   ldpc::check_args(pattern, rule, max_iter);
-  const size_t ib = nch * n_per_ch * 8;
-  const size_t cb = nch * max_cand * sizeof(SyncCandidate), nb = nch * sizeof(uint32_t);
   const size_t lb = nch * max_cand * kSyncLlr * sizeof(float);
+  const size_t cb = nch * max_cand * sizeof(SyncCandidate), nb = nch * sizeof(uint32_t);
   const size_t rb = nch * max_cand * sizeof(ldpc::Result), kb = nch * sizeof(DecodePick);
-  const size_t n_off = (cb + 15) / 16 * 16, k_off = (rb + 15) / 16 * 16;
-  h_iq_.resize(ib + 16);
+  const size_t n_off = cand_count_offset(nch, max_cand), k_off = (rb + 15) / 16 * 16;  // pick sits behind results
+  stage_in(h_iq_, iq, nch * n_per_ch * 8);
   h_cand_.resize(n_off + nb + 16);
   h_out_.resize(lb + 16);
   h_res_.resize(k_off + kb + 16);
-  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
-  char* cbase = h_cand_.as<char>();
-  char* rbase = h_res_.as<char>();
   decode(pattern, h_iq_.as<void>(), nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand, rule, max_iter,
-         reinterpret_cast<SyncCandidate*>(cbase), reinterpret_cast<uint32_t*>(cbase + n_off), h_out_.as<float>(), rbase,
-         reinterpret_cast<DecodePick*>(rbase + k_off), nullptr);
-  ORION_HIP(hipMemcpy(cand, cbase, cb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(count, cbase + n_off, nb, hipMemcpyDeviceToHost));
-  if (llr) ORION_HIP(hipMemcpy(llr, h_out_.as<void>(), lb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(results, rbase, rb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(pick, rbase + k_off, kb, hipMemcpyDeviceToHost));
+         h_cand_.as<SyncCandidate>(), reinterpret_cast<uint32_t*>(h_cand_.as<char>() + n_off), h_out_.as<float>(),
+         h_res_.as<void>(), reinterpret_cast<DecodePick*>(h_res_.as<char>() + k_off), nullptr);
+  stage_out(cand, h_cand_, cb);
+  stage_out(count, h_cand_, nb, n_off);
+  stage_out(llr, h_out_, lb);
+  stage_out(results, h_res_, rb);
+  stage_out(pick, h_res_, kb, k_off);
   ORION_HIP(hipDeviceSynchronize());
 }
 
 // ---- FT8 / FT4 modulators, slot synthesis and hard demodulators --------------------------
+namespace {
+void check_synth(int protocol, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch, size_t n) {
+  ftmod::check_signals(protocol, signals, tones, nsig, nch);
+  if (n > (1ull << 36)) throw std::invalid_argument("synth: more than 2^36 samples per channel");
+}
+}  // namespace
+
 FtSynth::~FtSynth() {
   if (done_) (void)hipEventDestroy(done_);
   if (pin_) (void)hipHostFree(pin_);
@@ -226,8 +231,7 @@ FtSynth::~FtSynth() {
 
 void FtSynth::run(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
                   size_t n, bool accumulate, void* iq, const f2* rot, hipStream_t s) {
-  ftmod::check_signals(protocol, signals, tones, nsig, nch);
-  if (n > (1ull << 36)) throw std::invalid_argument("synth: more than 2^36 samples per channel");
+  check_synth(protocol, signals, tones, nsig, nch, n);
   if (nch == 0 || n == 0) return;
   const size_t rb = nsig * sizeof(ftmod::SynthRecord), bytes = rb + (nch + 1) * sizeof(uint32_t);
   // the previous launch's copy out of the pinned plan and its reads of the device plan
@@ -259,10 +263,10 @@ void FtMod::modulate(const uint8_t* tones, size_t nframes, void* iq_dev, hipStre
   if (nframes > 0x7fffffffull) throw std::invalid_argument("modulate: more than 2^31 - 1 frames");
   sig_.resize(nframes);
   for (size_t f = 0; f < nframes; ++f) sig_[f] = ftmod::Signal{static_cast<uint32_t>(f), 0u, 0, base_hz_, gain_};
-  if (rf_hz_ != 0.0f && rot_.size() == 0) {  // the first device call: construction touches no device
+  if (rf_hz_ != 0.0f && rot_.empty()) {  // the first device call: construction touches no device
     std::vector<float> p(2 * frame_len());
     ftmod::rotator_table(rf_hz_, fs_, frame_len(), p.data());
-    rot_.upload(p.data(), p.size() * sizeof(float), s);
+    rot_.set(p, s);
   }
   synth_.run(protocol_, fs_, sig_.data(), tones, nframes, nframes, frame_len(), false, iq_dev,
              rf_hz_ != 0.0f ? rot_.as<f2>() : nullptr, s);
@@ -272,43 +276,45 @@ void FtMod::modulate_host(const uint8_t* tones, size_t nframes, void* iq) {
   const size_t ob = nframes * frame_len() * 8;
   h_out_.resize(ob + 16);
   modulate(tones, nframes, h_out_.as<void>(), nullptr);
-  if (ob) ORION_HIP(hipMemcpy(iq, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(iq, h_out_, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
 namespace {
 std::mutex g_synth_mu;
-FtSynth& shared_synth() {
-  static FtSynth* p = new FtSynth;  // never destroyed: no HIP call at process exit
-  return *p;
-}
 }  // namespace
 
 void ft_synth(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
               size_t n, bool accumulate, void* iq_dev, hipStream_t s) {
   std::lock_guard<std::mutex> lk(g_synth_mu);
-  shared_synth().run(protocol, fs, signals, tones, nsig, nch, n, accumulate, iq_dev, nullptr, s);
+  per_device<FtSynth>().run(protocol, fs, signals, tones, nsig, nch, n, accumulate, iq_dev, nullptr, s);
 }
 
 void ft_synth_host(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
                    size_t n, bool accumulate, void* iq) {
-  ftmod::check_signals(protocol, signals, tones, nsig, nch);  // before any device call
-  if (n > (1ull << 36)) throw std::invalid_argument("synth: more than 2^36 samples per channel");
+  check_synth(protocol, signals, tones, nsig, nch, n);  // before any device call
   const size_t ob = nch * n * 8;
-  DevBuf d(ob + 16);
-  if (accumulate && ob) ORION_HIP(hipMemcpy(d.as<void>(), iq, ob, hipMemcpyHostToDevice));
+  DevBuf d;
+  stage_in(d, accumulate ? iq : nullptr, ob);
   ft_synth(protocol, fs, signals, tones, nsig, nch, n, accumulate, d.as<void>(), nullptr);
-  if (ob) ORION_HIP(hipMemcpy(iq, d.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(iq, d, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
-void ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame, uint8_t* tones,
-              float* energies, hipStream_t s) {
+namespace {
+const ftmod::Proto& check_demod(int protocol, size_t nframes, size_t n_per_frame) {
   const ftmod::Proto& m = ftmod::proto(protocol);
   if (n_per_frame < static_cast<size_t>(m.frame_len()))
     throw std::invalid_argument("demodulate: fewer samples per frame than a frame (FT8: 151680, FT4: 60480)");
   if (nframes > kMaxCh || n_per_frame > (1ull << 40))
     throw std::invalid_argument("demodulate: nframes <= 65535, n_per_frame <= 2^40");
+  return m;
+}
+}  // namespace
+
+void ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame, uint8_t* tones,
+              float* energies, hipStream_t s) {
+  check_demod(protocol, nframes, n_per_frame);
   float w[2 * ftmod::kMaxTones];
   ftmod::demod_steps(protocol, fs, base_hz, w);
   launch_ft_demod(protocol == ftmod::kFt4, static_cast<const f2*>(iq), static_cast<int>(nframes),
@@ -317,11 +323,7 @@ void ft_demod(int protocol, float fs, float base_hz, const void* iq, size_t nfra
 
 void ft_demod_host(int protocol, float fs, float base_hz, const void* iq, size_t nframes, size_t n_per_frame,
                    uint8_t* tones, float* energies) {
-  const ftmod::Proto& m = ftmod::proto(protocol);
-  if (n_per_frame < static_cast<size_t>(m.frame_len()))
-    throw std::invalid_argument("demodulate: fewer samples per frame than a frame (FT8: 151680, FT4: 60480)");
-  if (nframes > kMaxCh || n_per_frame > (1ull << 40))
-    throw std::invalid_argument("demodulate: nframes <= 65535, n_per_frame <= 2^40");
+  const ftmod::Proto& m = check_demod(protocol, nframes, n_per_frame);  // before any device call
   if (nframes == 0) return;
   const size_t ib = nframes * n_per_frame * 8, tb = nframes * m.data, eb = energies ? nframes * m.total * m.tones * 4 : 0;
   StagedIn d_iq(iq, ib, 0);
@@ -337,36 +339,28 @@ void Sync::waterfall_host(const void* iq, float fs, float base_hz, float tone_sp
                           size_t num_syms, size_t num_tones, size_t time_offset, size_t nch, size_t n_per_ch,
                           int mode, float* mag) {
   check_grid(nch, num_syms, num_tones);
-  const size_t ib = nch * n_per_ch * 8, ob = nch * num_syms * num_tones * sizeof(float);
-  h_iq_.resize(ib + 16);
+  const size_t ob = nch * num_syms * num_tones * sizeof(float);
+  stage_in(h_iq_, iq, nch * n_per_ch * 8);
   h_out_.resize(ob + 16);
-  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
   waterfall(h_iq_.as<void>(), fs, base_hz, tone_spacing_hz, samples_per_sym, num_syms, num_tones, time_offset, nch,
             n_per_ch, mode, h_out_.as<float>(), nullptr);
-  if (ob) ORION_HIP(hipMemcpy(mag, h_out_.as<void>(), ob, hipMemcpyDeviceToHost));
+  stage_out(mag, h_out_, ob);
   ORION_HIP(hipDeviceSynchronize());
 }
 
 void Sync::sync_host(int pattern, const void* iq, size_t nch, size_t n_per_ch, float fs, float base_hz, float max_hz,
                      int t_min, int t_max, size_t max_cand, SyncCandidate* cand, uint32_t* count, float* llr) {
-  if (max_cand == 0) throw std::invalid_argument("max_cand == 0");
-  if (max_cand > kMaxCand) throw std::invalid_argument("max_cand above 65536");
-  if (nch < 1 || nch > kMaxCh) throw std::invalid_argument("sync: 1 <= nch <= 65535");
-  const size_t ib = nch * n_per_ch * 8;
+  check_slots(nch, max_cand);
   const size_t cb = nch * max_cand * sizeof(SyncCandidate), nb = nch * sizeof(uint32_t);
-  const size_t lb = nch * max_cand * kSyncLlr * sizeof(float);
-  const size_t c_off = 0, n_off = (cb + 15) / 16 * 16;
-  h_iq_.resize(ib + 16);
+  const size_t lb = nch * max_cand * kSyncLlr * sizeof(float), n_off = cand_count_offset(nch, max_cand);
+  stage_in(h_iq_, iq, nch * n_per_ch * 8);
   h_cand_.resize(n_off + nb + 16);
   h_out_.resize(lb + 16);
-  if (ib) ORION_HIP(hipMemcpy(h_iq_.as<void>(), iq, ib, hipMemcpyHostToDevice));
-  char* cbase = h_cand_.as<char>();
   sync(pattern, h_iq_.as<void>(), nch, n_per_ch, fs, base_hz, max_hz, t_min, t_max, max_cand,
-       reinterpret_cast<SyncCandidate*>(cbase + c_off), reinterpret_cast<uint32_t*>(cbase + n_off),
-       h_out_.as<float>(), nullptr);
-  ORION_HIP(hipMemcpy(cand, cbase + c_off, cb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(count, cbase + n_off, nb, hipMemcpyDeviceToHost));
-  ORION_HIP(hipMemcpy(llr, h_out_.as<void>(), lb, hipMemcpyDeviceToHost));
+       h_cand_.as<SyncCandidate>(), reinterpret_cast<uint32_t*>(h_cand_.as<char>() + n_off), h_out_.as<float>(), nullptr);
+  stage_out(cand, h_cand_, cb);
+  stage_out(count, h_cand_, nb, n_off);
+  stage_out(llr, h_out_, lb);
   ORION_HIP(hipDeviceSynchronize());
 }
 

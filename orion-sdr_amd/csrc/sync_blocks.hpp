@@ -27,6 +27,11 @@ struct SyncGeometry {
 };
 SyncGeometry sync_geometry(int pattern, float base_hz, float max_hz, int t_min, int t_max);
 
+// A host entry stages cand [nch][max_cand] and count [nch] in one device buffer: count's offset.
+inline size_t cand_count_offset(size_t nch, size_t max_cand) {
+  return (nch * max_cand * sizeof(SyncCandidate) + 15) / 16 * 16;
+}
+
 class Sync {
  public:
   // Symbol rows per lane of the waterfall kernel: 1, 2, 4 or 8; 0 = chosen per call
@@ -61,7 +66,7 @@ class Sync {
   int rows_for(size_t num_syms, size_t num_tones, size_t nch) const;
   int rows_ = 0;
   // the step table on the device and the geometry it was built for
-  DevBuf steps_;
+  DevTable steps_;
   float st_fs_ = 0, st_base_ = 0, st_spacing_ = 0;
   size_t st_tones_ = 0;
   DevBuf wf_, score_;             // sync()'s waterfall; the score map
@@ -88,9 +93,16 @@ void ldpc_decode_host(const float* llr, size_t n, const uint32_t* count, size_t 
 // previous launch, builds the plan on the host in pinned memory (signals and tones are host
 // memory), and queues the copy and the launch on s: asynchronous once the buffers have grown
 // to the plan. iq is device memory [nch][n] cf32. rot: kernels.hpp launch_ft_synth.
+// The mechanism is what blocks.hpp PlanUpload holds for the PSK31 entries. It stays spelt out
+// here: the time of orion_ft_synth_device is the host's plan build (ftmod::synth_plan_into),
+// which moves by tens of per cent with where a build places it (profiles/HISTORY.md), so an
+// A/B of this path against PlanUpload has not been able to show that the two are equal.
 class FtSynth {
  public:
+  FtSynth() = default;
   ~FtSynth();
+  FtSynth(const FtSynth&) = delete;
+  FtSynth& operator=(const FtSynth&) = delete;
   void run(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
            size_t n, bool accumulate, void* iq, const f2* rot, hipStream_t s);
 
@@ -115,11 +127,12 @@ class FtMod {
  private:
   int protocol_;
   float fs_, base_hz_, rf_hz_, gain_;
-  DevBuf rot_, h_out_;
+  DevTable rot_;
+  DevBuf h_out_;
   FtSynth synth_;
   std::vector<ftmod::Signal> sig_;
 };
-// Slot synthesis on a shared plan buffer (one call at a time, process-wide).
+// Slot synthesis on a shared FtSynth, one per device (one call at a time, process-wide).
 void ft_synth(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,
               size_t n, bool accumulate, void* iq_dev, hipStream_t s);
 void ft_synth_host(int protocol, float fs, const ftmod::Signal* signals, const uint8_t* tones, size_t nsig, size_t nch,

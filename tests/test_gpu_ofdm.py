@@ -217,6 +217,35 @@ def test_demod_kernel_exact(lib, torch, cp, backoff, eq):
     assert e_dev <= 2 * e_host
 
 
+@pytest.mark.parametrize("eq", ["training_symbol", "pilot_interp"])
+def test_tables_replaced_between_two_device_demodulate_calls(lib, torch, eq):
+    """n_fft 64, 2 symbols on device tensors: a demodulate call, then set_pilot_bins (the
+    pilots in another order with other values, one data bin fewer) and estimate_channel, then
+    the call again on the same handle. The first result has the bits of a fresh engine, the
+    second those of a fresh engine configured the same way before its first call."""
+    c, r = make_cfg(lib, "qam16")
+    iq = torch.from_numpy(rx_signal(lib, c, r, 1, 2, 61)).cuda()
+    tr = rand_c(np.random.default_rng(62), 64)
+    pilots = np.array([b % 64 for b in PILOT_IDX[::-1]], np.uint32)
+
+    def configure(d):
+        lib.OfdmEqualizer.set_pilot_bins(d, pilots, np.array([1j, 1, -1, -1j], np.complex64),
+                                         np.asarray(r.data_bins[1:], np.uint32))
+        d.estimate_channel_freq(tr)
+        return d
+
+    def run(d):
+        return [t.cpu().numpy() for t in lib.ofdm_demodulate_batch(d, iq, bits=True, llr=True)]
+
+    want_first, want_second = run(lib.OfdmDemod(c, eq)), run(configure(lib.OfdmDemod(c, eq)))
+    d = lib.OfdmDemod(c, eq)
+    first = lib.ofdm_demodulate_batch(d, iq, bits=True, llr=True)  # left in flight: no read back before the tables change
+    second = run(configure(d))
+    assert all(same(g.cpu().numpy(), w) for g, w in zip(first, want_first))
+    assert all(same(g, w) for g, w in zip(second, want_second))
+    assert not same(second[0], want_first[0])
+
+
 # ---- 3. the elementwise kernels -------------------------------------------------------------
 @pytest.mark.parametrize("order", R.ORDERS)
 def test_decider_and_llr_kernels_exact(lib, order):

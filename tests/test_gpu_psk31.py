@@ -460,6 +460,40 @@ def test_synth_sums_clipped_signals_within_the_closed_form_bound(gpu_lib):
         gpu_lib.psk31_synth(sig, bits[:3], n, nch=2, fs=FS)
 
 
+def test_synth_plans_and_modulator_batches_queued_back_to_back_on_one_stream(gpu_lib):
+    """Two psk31_synth plans (one signal of 2 bits; three signals on 2 channels) and two
+    batches of one modulator handle (2 streams of 3 symbols, 3 streams of 5) queued on one
+    non-default stream with nothing between them, read back after a single synchronise: every
+    plan is uploaded for its own launch, so each output has the bytes of the same call made
+    alone (a fresh modulator for each batch). This pins the results, not the ordering: plans
+    of a few hundred bytes are copied long before the next call rewrites the pinned space, so
+    the test would rarely fail if a call did not wait for the previous one."""
+    import torch
+
+    rng = np.random.default_rng(31)
+    n = 4 * SPS + 5
+    spec = [[(0, P.BPSK, 10, 1000.0, 1.0, 2)],
+            [(0, P.QPSK, -100, 1531.25, -0.5, 3), (1, P.BPSK, 300, 0.0, 0.7, 4), (0, P.BPSK, 37, 500.0, 0.25, 1)]]
+    plans = []
+    for rows in spec:
+        sig = np.zeros(len(rows), gpu_lib.PSK31_SIGNAL_DTYPE)
+        for k, (ch, mode, off, rf, gain, _) in enumerate(rows):
+            sig[k] = (ch, mode, off, rf, gain, 0)
+        plans.append((sig, [rng.integers(0, 2, r[5]).astype(np.uint8) for r in rows], 1 + max(r[0] for r in rows)))
+    batches = [rng.integers(0, 2, shape).astype(np.uint8) for shape in ((2, 3), (3, 5))]
+    alone = [gpu_lib.psk31_synth(sig, bits, n, nch=nch, fs=FS, device=True).cpu().numpy() for sig, bits, nch in plans]
+    alone += [gpu_lib.Qpsk31Mod(FS, 1000.0, 0.7).modulate_batch(b, device=True).cpu().numpy() for b in batches]
+    mod = gpu_lib.Qpsk31Mod(FS, 1000.0, 0.7)
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        got = [gpu_lib.psk31_synth(sig, bits, n, nch=nch, fs=FS, device=True) for sig, bits, nch in plans]
+        got += [mod.modulate_batch(b, device=True) for b in batches]
+    torch.cuda.synchronize()
+    for g, want in zip(got, alone):
+        assert g.cpu().numpy().tobytes() == want.tobytes()
+
+
 # ---- psk31_sync, the band browser and Psk31Stream ---------------------------------------------
 def _embed(iq, total):
     buf = np.zeros(total, np.complex64)

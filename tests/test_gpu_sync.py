@@ -276,3 +276,36 @@ def test_handle_reuse_across_geometries(gpu_lib):
         assert x.tobytes() == y.tobytes()
     for x, y in zip(b, fresh):
         assert x.tobytes() == y.tobytes()
+
+
+# ---- 7. the step table replaced under launches of another stream ------------------
+def test_step_table_is_replaced_whatever_streams_the_earlier_calls_used(gpu_lib):
+    """One engine on device tensors: geometry A (2 channels, 64 samples per symbol, 6
+    symbols, 9 tones 6.25 Hz apart) on one stream, geometry B (5 tones 20.833334 Hz apart
+    from another base) on a second stream with no host synchronisation between the
+    enqueues, then A again on the first. compute_waterfall reads the handle's step table
+    and no scratch, so the handle contract makes the three calls well defined; each gives
+    the bits of the same call made alone on a fresh engine. This pins the contract's results,
+    not the ordering: a launch this small ends long before the next table is uploaded, so
+    the test would rarely fail if the table's guard were removed."""
+    import torch
+
+    rng = np.random.default_rng(20)
+    sps, ns = 64, 6
+    x = (rng.standard_normal((2, sps * ns)) + 1j * rng.standard_normal((2, sps * ns))).astype(np.complex64)
+    xd = torch.from_numpy(x).cuda()
+    geom_a, geom_b = (FS, BASE, 6.25, sps, ns, 9), (FS, 1500.0, 20.833334, sps, ns, 5)
+    alone = [gpu_lib.SyncEngine().compute_waterfall(xd, *g).cpu().numpy() for g in (geom_a, geom_b)]
+    eng = gpu_lib.SyncEngine()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s1):
+        a1 = eng.compute_waterfall(xd, *geom_a)
+    with torch.cuda.stream(s2):
+        b = eng.compute_waterfall(xd, *geom_b)
+    with torch.cuda.stream(s1):
+        a2 = eng.compute_waterfall(xd, *geom_a)
+    torch.cuda.synchronize()
+    assert a1.shape == (2, ns, 9) and b.shape == (2, ns, 5)
+    for got, want in ((a1, alone[0]), (b, alone[1]), (a2, alone[0])):
+        assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32))

@@ -15,6 +15,10 @@ per channel, 0-3000 Hz, 10 candidates of 1024 bits, for the same channel counts:
 call, and the waterfall, the search and the candidates' demodulation each timed alone; beside
 the search, the library's host search on the downloaded waterfall, one thread.
 
+The synthesiser and modulator entries (orion_psk31_synth_device, modulate_batch on a device
+tensor): wall clock around one call and a synchronise, since their cost is the host's plan
+build, upload and launch; a small and a larger call of each.
+
 The batched QPSK31 Viterbi decode (k_psk31_viterbi) on
 device-resident soft symbols: 1, 64 and 4096 streams of 1024 symbols (coded random bits
 as DQPSK phasors plus Gaussian noise of deviation 0.5).
@@ -209,6 +213,47 @@ def run_sync(nch, n, warmup, reps, out):
     out.write(json.dumps(rec) + "\n")
 
 
+def wall_timed(fn, warmup, reps):
+    """Wall clock around one call and a synchronise, in microseconds: the host's part of an entry
+    (plan build, upload, launch) is what these entries cost, and device events do not see it."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        us.append((time.perf_counter() - t0) * 1e6)
+    return round(statistics.median(us), 1), round(min(us), 1)
+
+
+def run_entries(warmup, reps, out):
+    """psk31_synth and modulate_batch on device tensors: a small and a larger call of each."""
+    rng = np.random.default_rng(3)
+    fs, sps = 8000.0, 256
+    for nch, per_ch, nbits in ((1, 1, 64), (16, 8, 256)):
+        sig = np.zeros(nch * per_ch, orion_sdr.PSK31_SIGNAL_DTYPE)
+        for k in range(sig.size):
+            sig[k] = (k % nch, k % 2, 100 * k, 500.0 + 31.25 * k, 0.5, 0)
+        bits = [rng.integers(0, 2, nbits).astype(np.uint8) for _ in range(sig.size)]
+        n = (nbits + 8) * sps
+        buf = torch.zeros((nch, n), dtype=torch.complex64, device="cuda")
+        med, lo = wall_timed(lambda: orion_sdr.psk31_synth(sig, bits, n, nch=nch, fs=fs, out=buf), warmup, reps)
+        rec = {"case": "psk31_synth call", "nch": nch, "signals": int(sig.size), "n_bits": nbits, "reps": reps,
+               "wall_us_median": med, "wall_us_min": lo}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+    for ns, n in ((1, 64), (64, 256)):
+        b = rng.integers(0, 2, (ns, n)).astype(np.uint8)
+        m = orion_sdr.Qpsk31Mod(fs, 1000.0, 0.7)
+        med, lo = wall_timed(lambda: m.modulate_batch(b, device=True), warmup, reps)
+        rec = {"case": "psk31 modulate_batch call", "nstreams": ns, "n_bits": n, "reps": reps, "wall_us_median": med,
+               "wall_us_min": lo}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "psk31_bench.jsonl"))
@@ -235,3 +280,4 @@ if __name__ == "__main__":
             run_sync(nch, a.samples, a.warmup, max(20, a.reps), out)
         for n in a.sizes:
             run_viterbi(n, a.n_syms, 0.5, a.warmup, max(20, a.reps), a.host_streams, out)
+        run_entries(a.warmup, max(50, a.reps), out)
