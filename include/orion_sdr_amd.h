@@ -1465,6 +1465,99 @@ int orion_ofdm_acquire_weights_device(orion_ofdm_acquire* a, const void* rows, s
 int orion_ofdm_equalize_track_device(orion_ofdm* h, const void* raw, const void* weights, size_t frames, size_t n_symbols,
                                      void* syms, float* llr, void* stream);
 
+/* ---- The DVB-T 2K frame (src/waveform/dvb_t.rs, dvb_t_tps.rs, src/sync/dvb_t_gi_sync.rs,
+ * src/modulate/dvb_t_frame.rs, src/demodulate/dvb_t_frame.rs) -------------------------------
+ * n_fft = 2048, 1705 active carriers, 1512 data carriers in each of the four scattered-pilot
+ * phases (symbol mod 4). guard: 0..3 = 1/32, 1/16, 1/8, 1/4 (cp_len 64 .. 512). Bits are uint8,
+ * one per byte; v is the bits per carrier (2, 4, 6). The *_host entries touch no device and
+ * run the reference's f32 operation order; the *_device entries take device pointers, are
+ * asynchronous on stream, keep no state between calls and give the host entries' bits
+ * (cfo_hz: the device's atan2f). ORION_E_ARG for a value outside these ranges. */
+#define ORION_DVBT_N_FFT 2048
+#define ORION_DVBT_DATA_CARRIERS 1512
+#define ORION_DVBT_TPS_CARRIERS 17
+#define ORION_DVBT_CONTINUAL_PILOTS 45
+#define ORION_DVBT_TPS_SYMBOLS 68
+#define ORION_DVBT_MAX_REF_PILOTS 193
+#define ORION_DVBT_MAX_RX_WINDOW_BACKOFF 85
+/* The constants: continual [45] and tps [17] active-carrier indices (Tables 7 and 8), their
+ * transform bins, wk [1705] the reference sequence; any pointer may be NULL. */
+int orion_dvbt_constants(uint32_t* continual, uint32_t* tps, uint32_t* continual_bins, uint32_t* tps_bins, uint8_t* wk);
+float orion_dvbt_boosted_pilot_value(uint8_t wk);
+/* One phase of dvb_t_2k_plans: data_bins [1512] (active-carrier order), pilot_bins / pilot_vals
+ * [n_pilots] every reserved carrier with its boosted value (real), ref_bins / ref_vals [n_ref]
+ * the channel references (pilots minus TPS) sorted by bin; role [2048] (>= 0 the data index,
+ * -1 null, -2 / -3 a pilot + / -, -4 - j TPS carrier j). Arrays hold 1512 / 256 / 256 / 2048. */
+int orion_dvbt_phase(int phase, uint32_t* data_bins, uint32_t* pilot_bins, float* pilot_vals, size_t* n_pilots,
+                     uint32_t* ref_bins, float* ref_vals, size_t* n_ref, int32_t* role);
+/* dvb_t_map_symbol / dvb_t_demap_symbol / dvb_t_soft_llr over n symbols: bits and llr
+ * [n][v], syms [n] cf32. */
+int orion_dvbt_map_host(const uint8_t* bits, size_t n, size_t v, void* syms);
+int orion_dvbt_demap_host(const void* syms, size_t n, size_t v, uint8_t* bits);
+int orion_dvbt_llr_host(const void* syms, size_t n, size_t v, float* llr);
+/* tps_bch_encode: info [53] -> codeword [67]; tps_bch_decode: codeword [67] -> info [53],
+ * *ok = 0 where the reference returns None. */
+int orion_dvbt_tps_bch_encode(const uint8_t* info, uint8_t* codeword);
+int orion_dvbt_tps_bch_decode(const uint8_t* codeword, uint8_t* info, int* ok);
+/* TpsWord::pack / unpack: fields [5] = frame_number, constellation (ORION_OFDM_QPSK / QAM16 /
+ * QAM64), code rate (ORION_FEC_RATE_*), guard, cell_id; bits [68] s0 .. s67. */
+int orion_dvbt_tps_pack(const int32_t* fields, uint8_t* bits);
+int orion_dvbt_tps_unpack(const uint8_t* bits, int32_t* fields, int* ok);
+/* TpsEncoder over n_symbols (reset after every 68th): cells [n_symbols][17] cf32.
+ * TpsDecoder::feed_symbol over the first min(n_symbols, 68) symbols: bits [68], *n_bits. */
+int orion_dvbt_tps_encode_host(const uint8_t* bits, size_t n_symbols, void* cells);
+int orion_dvbt_tps_decide_host(const void* cells, size_t n_symbols, uint8_t* bits, size_t* n_bits);
+/* dvb_t_gi_sync_with. |gamma| is defined as the f32 rounding of the f64 square root of the f64
+ * sum of the two exact f64 squares (not libm's hypotf). out [5] f32: cfo_hz, score, gamma.re,
+ * gamma.im, phi; *found = 0 where the reference returns None. metric (may be NULL) [search_len]. */
+int orion_dvbt_gi_sync_host(const void* iq, size_t n, size_t n_fft, size_t cp_len, float fs, size_t search_len, float rho,
+                            size_t max_symbols, float origin_score_ratio, int64_t* start, float* out, int* found,
+                            float* metric);
+/* dvb_t_integer_cfo over one symbol's bins freq [n_fft] cf32. */
+int orion_dvbt_integer_cfo_host(const void* freq, size_t n_freq, size_t n_fft, int max_bins, int32_t* bins,
+                                float* confidence, int* found);
+/* The frame modulator from the coded bits on (modulate/dvb_t_frame.rs:213-261): bits [n_bits],
+ * tps [68] -> iq [n_symbols (2048 + cp_len)] cf32; a data carrier whose bits lie past n_bits is
+ * zero. The frame demodulator's symbol loop (demodulate/dvb_t_frame.rs:497-583) from the
+ * acquired start: iq [n_symbols (2048 + cp_len)] -> llr [n_symbols][1512 v], cells
+ * [n_symbols][17] cf32 (raw bins), syms (may be NULL) [n_symbols][1512] cf32. */
+int orion_dvbt_mod_symbols_host(const uint8_t* bits, size_t n_bits, size_t v, size_t cp_len, const uint8_t* tps,
+                                size_t n_symbols, size_t roll_off, void* iq);
+int orion_dvbt_demod_symbols_host(const void* iq, size_t n_symbols, size_t cp_len, size_t backoff, size_t v, float* llr,
+                                  void* cells, void* syms);
+/* k_dvbt_mod, one workgroup per (frame, symbol): bits [frames][row_bits], nbits [frames] i32
+ * (NULL: row_bits each), tps [frames][3] u32 (bit l of the 68-bit word is s_l) -> iq
+ * [frames][n_symbols (2048 + cp_len)]. frames <= 65535. */
+int orion_dvbt_mod_symbols_device(const uint8_t* bits, size_t frames, size_t row_bits, const int32_t* nbits,
+                                  const uint32_t* tps, size_t v, size_t cp_len, size_t n_symbols, size_t roll_off,
+                                  void* iq, void* stream);
+/* k_gi_metric + k_gi_select, one independent search per capture of iq [ncap][n]: per capture
+ * start, found (i32), score, cfo_hz, phi (f32), gamma (cf32); per offset metric, phi_all (f32)
+ * and gamma_all (cf32), each [ncap][search_len]. ncap <= 65535, n < 2^31. */
+typedef struct {
+  int32_t* start;
+  int32_t* found;
+  float* score;
+  float* cfo_hz;
+  void* gamma;
+  float* phi;
+  float* metric;
+  void* gamma_all;
+  float* phi_all;
+} orion_dvbt_gi_out;
+int orion_dvbt_gi_sync_batch_device(const void* iq, size_t ncap, size_t n, size_t n_fft, size_t cp_len, float fs,
+                                    size_t search_len, float rho, size_t max_symbols, float origin_score_ratio,
+                                    const orion_dvbt_gi_out* out, void* stream);
+/* k_dvbt_demod: iq [ncap][n] from start[c]; a capture with found[c] == 0 or whose frame does
+ * not fit is skipped and its outputs are left as they are. Shapes as the host entry's per capture. */
+int orion_dvbt_demod_symbols_device(const void* iq, size_t ncap, size_t n, const int32_t* start, const int32_t* found,
+                                    size_t n_symbols, size_t cp_len, size_t backoff, size_t v, float* llr, void* cells,
+                                    void* syms, void* stream);
+/* k_tps_decode, one wave per frame: cells [frames][n_symbols][17] -> fields [frames][5] i32 (as
+ * orion_dvbt_tps_unpack) and status [frames] i32 (0 decoded, 1 not). */
+int orion_dvbt_tps_decode_device(const void* cells, size_t frames, size_t n_symbols, int32_t* fields, int32_t* status,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@
 #include "bch.hpp"
 #include "bch_blocks.hpp"
 #include "blocks.hpp"
+#include "dvbt.hpp"
+#include "dvbt_blocks.hpp"
 #include "fec.hpp"
 #include "fec_blocks.hpp"
 #include "frame.hpp"
@@ -2810,6 +2812,212 @@ int orion_ofdm_equalize_track_device(orion_ofdm* h, const void* raw, const void*
   if (frames && n_symbols && (!raw || !weights || !syms)) return fail(ORION_E_NULL, "null buffer");
   return guarded([&] {
     h->impl.equalize_track(raw, weights, frames, n_symbols, syms, llr, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+
+// ---- the DVB-T 2K frame (dvbt.hpp, dvbt_blocks.hpp) ----
+static_assert(ORION_DVBT_N_FFT == orion::dvbt::kNFft && ORION_DVBT_DATA_CARRIERS == orion::dvbt::kData &&
+                  ORION_DVBT_TPS_CARRIERS == orion::dvbt::kTps && ORION_DVBT_CONTINUAL_PILOTS == orion::dvbt::kContinual &&
+                  ORION_DVBT_TPS_SYMBOLS == orion::dvbt::kTpsSymbols && ORION_DVBT_MAX_REF_PILOTS == orion::dvbt::kMaxRefPilots &&
+                  ORION_DVBT_MAX_RX_WINDOW_BACKOFF == orion::dvbt::kMaxRxWindowBackoff &&
+                  sizeof(orion_dvbt_gi_out) == sizeof(orion::GiOut),
+              "the header's DVB-T constants are dvbt.hpp's");
+static bool dvbt_v_ok(size_t v) { return v == 2 || v == 4 || v == 6; }
+int orion_dvbt_constants(uint32_t* continual, uint32_t* tps, uint32_t* continual_bins, uint32_t* tps_bins, uint8_t* wk) {
+  return guarded([&] {
+    const orion::dvbt::Tables& t = orion::dvbt::tables();
+    for (size_t i = 0; i < orion::dvbt::kContinual; ++i) {
+      if (continual) continual[i] = orion::dvbt::kContinualPilots2k[i];
+      if (continual_bins) continual_bins[i] = t.continual_bins[i];
+    }
+    for (size_t i = 0; i < orion::dvbt::kTps; ++i) {
+      if (tps) tps[i] = orion::dvbt::kTpsCarriers2k[i];
+      if (tps_bins) tps_bins[i] = t.tps_bins[i];
+    }
+    if (wk) {
+      const std::vector<uint8_t> w = orion::dvbt::wk_prbs(orion::dvbt::kActive);
+      std::memcpy(wk, w.data(), w.size());
+    }
+    return ORION_OK;
+  });
+}
+float orion_dvbt_boosted_pilot_value(uint8_t wk) { return orion::dvbt::boosted_pilot_value(wk); }
+int orion_dvbt_phase(int phase, uint32_t* data_bins, uint32_t* pilot_bins, float* pilot_vals, size_t* n_pilots,
+                     uint32_t* ref_bins, float* ref_vals, size_t* n_ref, int32_t* role) {
+  if (phase < 0 || phase > 3) return fail(ORION_E_ARG, "dvbt: phase is 0..3");
+  return guarded([&] {
+    const orion::dvbt::Phase& p = orion::dvbt::tables().phase[phase];
+    if (data_bins) std::copy(p.data_bins.begin(), p.data_bins.end(), data_bins);
+    if (pilot_bins) std::copy(p.pilot_bins.begin(), p.pilot_bins.end(), pilot_bins);
+    if (pilot_vals) std::copy(p.pilot_val.begin(), p.pilot_val.end(), pilot_vals);
+    if (n_pilots) *n_pilots = p.pilot_bins.size();
+    if (ref_bins) std::copy(p.ref_bins.begin(), p.ref_bins.end(), ref_bins);
+    if (ref_vals) std::copy(p.ref_val.begin(), p.ref_val.end(), ref_vals);
+    if (n_ref) *n_ref = p.ref_bins.size();
+    if (role) std::copy(p.role.begin(), p.role.end(), role);
+    return ORION_OK;
+  });
+}
+int orion_dvbt_map_host(const uint8_t* bits, size_t n, size_t v, void* syms) {
+  if (!dvbt_v_ok(v)) return fail(ORION_E_ARG, "dvbt: v is 2, 4 or 6");
+  if (n && (!bits || !syms)) return fail(ORION_E_NULL, "null buffer");
+  float* s = static_cast<float*>(syms);
+  for (size_t i = 0; i < n; ++i) orion::dvbt::map_symbol(bits + i * v, v, s + 2 * i, s + 2 * i + 1);
+  return ORION_OK;
+}
+int orion_dvbt_demap_host(const void* syms, size_t n, size_t v, uint8_t* bits) {
+  if (!dvbt_v_ok(v)) return fail(ORION_E_ARG, "dvbt: v is 2, 4 or 6");
+  if (n && (!bits || !syms)) return fail(ORION_E_NULL, "null buffer");
+  const float* s = static_cast<const float*>(syms);
+  for (size_t i = 0; i < n; ++i) orion::dvbt::demap_symbol(s[2 * i], s[2 * i + 1], v, bits + i * v);
+  return ORION_OK;
+}
+int orion_dvbt_llr_host(const void* syms, size_t n, size_t v, float* llr) {
+  if (!dvbt_v_ok(v)) return fail(ORION_E_ARG, "dvbt: v is 2, 4 or 6");
+  if (n && (!llr || !syms)) return fail(ORION_E_NULL, "null buffer");
+  const float* s = static_cast<const float*>(syms);
+  for (size_t i = 0; i < n; ++i) orion::dvbt::soft_llr(s[2 * i], s[2 * i + 1], v, llr + i * v);
+  return ORION_OK;
+}
+int orion_dvbt_tps_bch_encode(const uint8_t* info, uint8_t* codeword) {
+  if (!info || !codeword) return fail(ORION_E_NULL, "null buffer");
+  orion::dvbt::tps_bch_encode(info, codeword);
+  return ORION_OK;
+}
+int orion_dvbt_tps_bch_decode(const uint8_t* codeword, uint8_t* info, int* ok) {
+  if (!info || !codeword || !ok) return fail(ORION_E_NULL, "null buffer");
+  *ok = orion::dvbt::tps_bch_decode(codeword, info) ? 1 : 0;
+  return ORION_OK;
+}
+int orion_dvbt_tps_pack(const int32_t* fields, uint8_t* bits) {
+  if (!fields || !bits) return fail(ORION_E_NULL, "null buffer");
+  if (fields[0] < 0 || fields[0] > 3 || fields[1] < ORION_OFDM_QPSK || fields[1] > ORION_OFDM_QAM64 || fields[2] < 0 ||
+      fields[2] > 4 || fields[3] < 0 || fields[3] > 3 || fields[4] < 0 || fields[4] > 255)
+    return fail(ORION_E_ARG, "dvbt: a TPS field out of range");
+  orion::dvbt::TpsWord w;
+  w.frame_number = fields[0];
+  w.constellation = fields[1];
+  w.code_rate = fields[2];
+  w.guard = fields[3];
+  w.cell_id = fields[4];
+  orion::dvbt::tps_pack(w, bits);
+  return ORION_OK;
+}
+int orion_dvbt_tps_unpack(const uint8_t* bits, int32_t* fields, int* ok) {
+  if (!fields || !bits || !ok) return fail(ORION_E_NULL, "null buffer");
+  orion::dvbt::TpsWord w;
+  *ok = orion::dvbt::tps_unpack(bits, &w) ? 1 : 0;
+  const int32_t f[5] = {w.frame_number, w.constellation, w.code_rate, w.guard, w.cell_id};
+  for (int i = 0; i < 5; ++i) fields[i] = *ok ? f[i] : 0;
+  return ORION_OK;
+}
+int orion_dvbt_tps_encode_host(const uint8_t* bits, size_t n_symbols, void* cells) {
+  if (!bits || (n_symbols && !cells)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    const orion::dvbt::Tables& t = orion::dvbt::tables();
+    std::vector<float> signs(n_symbols);
+    orion::dvbt::tps_symbol_signs(bits, n_symbols, signs.data());
+    float* c = static_cast<float*>(cells);
+    for (size_t l = 0; l < n_symbols; ++l)
+      for (size_t j = 0; j < orion::dvbt::kTps; ++j) {
+        c[2 * (l * orion::dvbt::kTps + j)] = signs[l] * t.tps_sign[j];
+        c[2 * (l * orion::dvbt::kTps + j) + 1] = 0.0f;
+      }
+    return ORION_OK;
+  });
+}
+int orion_dvbt_tps_decide_host(const void* cells, size_t n_symbols, uint8_t* bits, size_t* n_bits) {
+  if (!bits || !n_bits || (n_symbols && !cells)) return fail(ORION_E_NULL, "null buffer");
+  *n_bits = orion::dvbt::tps_decide(static_cast<const float*>(cells), n_symbols, bits);
+  return ORION_OK;
+}
+int orion_dvbt_gi_sync_host(const void* iq, size_t n, size_t n_fft, size_t cp_len, float fs, size_t search_len, float rho,
+                            size_t max_symbols, float origin_score_ratio, int64_t* start, float* out, int* found,
+                            float* metric) {
+  if (!start || !out || !found || (n && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt::GiConfig cfg;
+    cfg.rho = rho;
+    cfg.max_symbols = max_symbols;
+    cfg.origin_score_ratio = origin_score_ratio;
+    orion::dvbt::GiResult r;
+    *found = orion::dvbt::gi_sync(static_cast<const float*>(iq), n, n_fft, cp_len, fs, search_len, cfg, &r, metric) ? 1 : 0;
+    *start = *found ? static_cast<int64_t>(r.start) : 0;
+    const float o[5] = {r.cfo_hz, r.score, r.gamma_re, r.gamma_im, r.phi};
+    for (int i = 0; i < 5; ++i) out[i] = *found ? o[i] : 0.0f;
+    return ORION_OK;
+  });
+}
+int orion_dvbt_integer_cfo_host(const void* freq, size_t n_freq, size_t n_fft, int max_bins, int32_t* bins,
+                                float* confidence, int* found) {
+  if (!bins || !found || (n_freq && !freq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    *bins = 0;
+    *found = orion::dvbt::integer_cfo(static_cast<const float*>(freq), n_freq, n_fft, max_bins, bins, confidence) ? 1 : 0;
+    return ORION_OK;
+  });
+}
+int orion_dvbt_mod_symbols_host(const uint8_t* bits, size_t n_bits, size_t v, size_t cp_len, const uint8_t* tps,
+                                size_t n_symbols, size_t roll_off, void* iq) {
+  if (!tps || (n_bits && !bits) || (n_symbols && !iq)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt::mod_symbols(bits, n_bits, v, cp_len, tps, n_symbols, roll_off, static_cast<float*>(iq));
+    return ORION_OK;
+  });
+}
+int orion_dvbt_demod_symbols_host(const void* iq, size_t n_symbols, size_t cp_len, size_t backoff, size_t v, float* llr,
+                                  void* cells, void* syms) {
+  if (n_symbols && (!iq || !llr || !cells)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt::demod_symbols(static_cast<const float*>(iq), n_symbols, cp_len, backoff, v, llr, static_cast<float*>(cells),
+                               static_cast<float*>(syms));
+    return ORION_OK;
+  });
+}
+int orion_dvbt_mod_symbols_device(const uint8_t* bits, size_t frames, size_t row_bits, const int32_t* nbits,
+                                  const uint32_t* tps, size_t v, size_t cp_len, size_t n_symbols, size_t roll_off,
+                                  void* iq, void* stream) {
+  if (frames && n_symbols && (!tps || !iq || (row_bits && !bits))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt_mod_symbols(bits, frames, row_bits, nbits, tps, v, cp_len, n_symbols, roll_off, iq,
+                            static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_dvbt_gi_sync_batch_device(const void* iq, size_t ncap, size_t n, size_t n_fft, size_t cp_len, float fs,
+                                    size_t search_len, float rho, size_t max_symbols, float origin_score_ratio,
+                                    const orion_dvbt_gi_out* out, void* stream) {
+  if (!out || (ncap && n && !iq)) return fail(ORION_E_NULL, "null buffer");
+  const void* const* f = reinterpret_cast<const void* const*>(out);
+  for (size_t k = 0; k < sizeof(orion_dvbt_gi_out) / sizeof(void*); ++k)
+    if (ncap && !f[k]) return fail(ORION_E_NULL, "null output");
+  return guarded([&] {
+    orion::GiOut o;
+    std::memcpy(&o, out, sizeof(o));
+    orion::dvbt::GiConfig cfg;
+    cfg.rho = rho;
+    cfg.max_symbols = max_symbols;
+    cfg.origin_score_ratio = origin_score_ratio;
+    orion::dvbt_gi_sync_batch(iq, ncap, n, n_fft, cp_len, fs, search_len, cfg, o, static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_dvbt_demod_symbols_device(const void* iq, size_t ncap, size_t n, const int32_t* start, const int32_t* found,
+                                    size_t n_symbols, size_t cp_len, size_t backoff, size_t v, float* llr, void* cells,
+                                    void* syms, void* stream) {
+  if (ncap && n_symbols && (!iq || !start || !found || !llr || !cells)) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt_demod_symbols(iq, ncap, n, start, found, n_symbols, cp_len, backoff, v, llr, cells, syms,
+                              static_cast<hipStream_t>(stream));
+    return ORION_OK;
+  });
+}
+int orion_dvbt_tps_decode_device(const void* cells, size_t frames, size_t n_symbols, int32_t* fields, int32_t* status,
+                                 void* stream) {
+  if (frames && (!fields || !status || (n_symbols && !cells))) return fail(ORION_E_NULL, "null buffer");
+  return guarded([&] {
+    orion::dvbt_tps_decode(cells, frames, n_symbols, fields, status, static_cast<hipStream_t>(stream));
     return ORION_OK;
   });
 }

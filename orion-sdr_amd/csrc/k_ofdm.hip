@@ -6,7 +6,7 @@
 //
 // The transform. One symbol lives in LDS; kOfdmThreads / T symbols share a workgroup, T =
 // min(n / 4, kOfdmThreads) lanes each, so that a workgroup's four waves are full at every
-// size. fft_lds is radix-2 decimation in time, two stages fused per pass: a lane holds the
+// size. fft_lds (ofdm_dev.hpp) is radix-2 decimation in time, two stages fused per pass: a lane holds the
 // four values of a radix-4 butterfly in registers, so a pass costs one LDS read and one LDS
 // write per value where two radix-2 passes cost two; a first radix-2 pass when log2 n is
 // odd. The arithmetic of each fused stage is the host's (ofdm.cpp fft_inplace): the same
@@ -28,54 +28,6 @@
 namespace orion {
 
 namespace {
-__device__ __forceinline__ int pad(int p) { return p + (p >> 5); }
-__device__ __forceinline__ int brev(int k, int log2n) { return static_cast<int>(__brev(static_cast<unsigned>(k)) >> (32 - log2n)); }
-// b w, the host's butterfly product.
-__device__ __forceinline__ f2 twmul(f2 d, f2 w) { return f2{d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x}; }
-__device__ __forceinline__ f2 twid(const f2* __restrict__ tw, int k, bool inv) {
-  f2 w = tw[k];
-  if (inv) w.y = -w.y;
-  return w;
-}
-
-// In place over x (one symbol, bit-reversed order in, natural order out). Every lane of the
-// workgroup calls it (the barriers are the workgroup's); t < T indexes the symbol's lanes.
-__device__ __forceinline__ void fft_lds(f2* x, int n, int log2n, const f2* __restrict__ tw, bool inv, int t, int T) {
-  int cur = 1;  // the size of the transforms already done
-  if (log2n & 1) {
-    __syncthreads();
-    const f2 w = twid(tw, 0, inv);
-    for (int q = t; q < (n >> 1); q += T) {
-      const f2 a = x[pad(2 * q)], tt = twmul(x[pad(2 * q + 1)], w);
-      x[pad(2 * q)] = a + tt;
-      x[pad(2 * q + 1)] = a - tt;
-    }
-    cur = 2;
-  }
-  while (cur < n) {  // the stages of size len = 2 cur and 2 len in one pass
-    __syncthreads();
-    const int len = 2 * cur, half = cur, step = n / len;
-    for (int q = t; q < (n >> 2); q += T) {
-      const int j = q & (half - 1);
-      const int base = ((q - j) << 2) + j;
-      const f2 x0 = x[pad(base)], x1 = x[pad(base + half)], x2 = x[pad(base + len)], x3 = x[pad(base + len + half)];
-      // the stage of size len: pairs (x0, x1) and (x2, x3), both at offset j
-      const f2 w1 = twid(tw, j * step, inv);
-      const f2 t1 = twmul(x1, w1), t3 = twmul(x3, w1);
-      const f2 y0 = x0 + t1, y1 = x0 - t1, y2 = x2 + t3, y3 = x2 - t3;
-      // the stage of size 2 len: pairs (y0, y2) at offset j and (y1, y3) at offset j + half
-      const f2 t2 = twmul(y2, twid(tw, j * (step >> 1), inv));
-      const f2 t4 = twmul(y3, twid(tw, (j + half) * (step >> 1), inv));
-      x[pad(base)] = y0 + t2;
-      x[pad(base + len)] = y0 - t2;
-      x[pad(base + half)] = y1 + t4;
-      x[pad(base + len + half)] = y1 - t4;
-    }
-    cur <<= 2;
-  }
-  __syncthreads();
-}
-
 // The estimate at bin from np > 0 bin-sorted pilots; rx(bin) is the received value of a bin.
 // The two bracketing pilots' ratios are computed here, per bin, by binary search as the
 // reference does; no ratio table is kept between bins.

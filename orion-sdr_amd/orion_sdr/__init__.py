@@ -5841,3 +5841,869 @@ class OfdmFrameStreamDemod:
                 return out
             self._buf = np.ascontiguousarray(self._buf[step.consume_to:])
             out.append(step)
+
+
+# ---- the DVB-T 2K frame: Figure-9a constellation, the four-phase pilot / TPS grid, the TPS word,
+# guard-interval acquisition, DvbTFrameMod / DvbTFrameDemod (src/waveform/dvb_t.rs, dvb_t_tps.rs,
+# src/sync/dvb_t_gi_sync.rs, src/modulate/dvb_t_frame.rs, src/demodulate/dvb_t_frame.rs) ----
+class _GiOutC(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("start", "found", "score", "cfo_hz", "gamma", "phi", "metric", "gamma_all",
+                                          "phi_all")]
+
+
+def _dvbt_sigs():
+    vp, sz, f, i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
+    pi, psz = C.POINTER(C.c_int), C.POINTER(C.c_size_t)
+    sig = {
+        "orion_dvbt_constants": (i, [vp, vp, vp, vp, vp]),
+        "orion_dvbt_boosted_pilot_value": (f, [C.c_uint8]),
+        "orion_dvbt_phase": (i, [i, vp, vp, vp, psz, vp, vp, psz, vp]),
+        "orion_dvbt_map_host": (i, [vp, sz, sz, vp]), "orion_dvbt_demap_host": (i, [vp, sz, sz, vp]),
+        "orion_dvbt_llr_host": (i, [vp, sz, sz, vp]),
+        "orion_dvbt_tps_bch_encode": (i, [vp, vp]), "orion_dvbt_tps_bch_decode": (i, [vp, vp, pi]),
+        "orion_dvbt_tps_pack": (i, [vp, vp]), "orion_dvbt_tps_unpack": (i, [vp, vp, pi]),
+        "orion_dvbt_tps_encode_host": (i, [vp, sz, vp]), "orion_dvbt_tps_decide_host": (i, [vp, sz, vp, psz]),
+        "orion_dvbt_gi_sync_host": (i, [vp, sz, sz, sz, f, sz, f, sz, f, C.POINTER(C.c_int64), vp, pi, vp]),
+        "orion_dvbt_integer_cfo_host": (i, [vp, sz, sz, i, C.POINTER(C.c_int32), C.POINTER(f), pi]),
+        "orion_dvbt_mod_symbols_host": (i, [vp, sz, sz, sz, vp, sz, sz, vp]),
+        "orion_dvbt_demod_symbols_host": (i, [vp, sz, sz, sz, sz, vp, vp, vp]),
+        "orion_dvbt_mod_symbols_device": (i, [vp, sz, sz, vp, vp, sz, sz, sz, sz, vp, vp]),
+        "orion_dvbt_gi_sync_batch_device": (i, [vp, sz, sz, sz, sz, f, sz, f, sz, f, C.POINTER(_GiOutC), vp]),
+        "orion_dvbt_demod_symbols_device": (i, [vp, sz, sz, vp, vp, sz, sz, sz, sz, vp, vp, vp, vp]),
+        "orion_dvbt_tps_decode_device": (i, [vp, sz, sz, vp, vp, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(_L, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+_dvbt_sigs()
+DVB_T_N_FFT, DVB_T_KMAX, DVB_T_ACTIVE_CARRIERS, DVB_T_DATA_CARRIERS = 2048, 1704, 1705, 1512
+DVB_T_SCATTERED_PHASES, DVB_T_SCATTERED_PILOT_SPACING, DVB_T_MAX_RX_WINDOW_BACKOFF = 4, 12, 85
+TPS_CODEWORD_BITS, TPS_INFO_BITS, TPS_PARITY_BITS, TPS_CARRIER_COUNT, TPS_SYMBOLS_PER_FRAME = 67, 53, 14, 17, 68
+TPS_SYNC_WORD_13, TPS_SYNC_WORD_24 = 0x35EE, 0xCA11
+DVB_T_GUARDS = {"1/32": 0, "1/16": 1, "1/8": 2, "1/4": 3}
+DVB_T_RX_ERRORS = {"acquisition": 1, "incomplete": 2, "tps_decode": 3, "payload_decode": 4}
+_DVBT_ORDERS = {"qpsk": 1, "qam16": 2, "qam64": 3}
+INTEGER_CFO_ACCUM_SYMBOLS, INTEGER_CFO_MAX_BINS = 8, 32
+__all__ += ["DVB_T_N_FFT", "DVB_T_KMAX", "DVB_T_ACTIVE_CARRIERS", "DVB_T_DATA_CARRIERS", "DVB_T_SCATTERED_PHASES",
+            "DVB_T_SCATTERED_PILOT_SPACING", "DVB_T_MAX_RX_WINDOW_BACKOFF", "TPS_CODEWORD_BITS", "TPS_INFO_BITS",
+            "TPS_PARITY_BITS", "TPS_CARRIER_COUNT", "TPS_SYMBOLS_PER_FRAME", "TPS_SYNC_WORD_13", "TPS_SYNC_WORD_24",
+            "DVB_T_GUARDS", "DVB_T_RX_ERRORS", "DVB_T_CONTINUAL_PILOTS_2K", "DVB_T_TPS_CARRIERS_2K", "wk_prbs",
+            "boosted_pilot_value", "dvb_t_cp_len_2k", "scattered_pilot_indices", "tps_carrier_bins",
+            "continual_pilot_bins", "dvb_t_2k_plans", "dvb_t_map_symbol", "dvb_t_demap_symbol", "dvb_t_soft_llr",
+            "tps_bch_encode", "tps_bch_decode", "TpsWord", "TpsEncoder", "TpsDecoder", "GiSyncConfig", "GiSyncResult",
+            "dvb_t_gi_sync", "dvb_t_gi_sync_with", "dvb_t_gi_refine", "dvb_t_gi_metric", "dvb_t_integer_cfo",
+            "dvb_t_mod_symbols", "dvb_t_demod_symbols", "dvb_t_mod_symbols_batch", "dvb_t_gi_sync_batch",
+            "dvb_t_demod_symbols_batch", "dvb_t_tps_decode_batch", "DvbTFrameParams", "DvbTFrame", "DvbTFrameMod",
+            "DvbTRxError", "DvbTRxFrame", "DvbTFrameDemod"]
+
+
+def _dvbt_constants():
+    cont, tps = np.zeros(45, np.uint32), np.zeros(17, np.uint32)
+    cb, tb, wk = np.zeros(45, np.uint32), np.zeros(17, np.uint32), np.zeros(DVB_T_ACTIVE_CARRIERS, np.uint8)
+    _check(_L.orion_dvbt_constants(cont.ctypes.data, tps.ctypes.data, cb.ctypes.data, tb.ctypes.data, wk.ctypes.data))
+    return cont, tps, cb, tb, wk
+
+
+def _dvbt_guard(guard) -> int:
+    g = DVB_T_GUARDS.get(guard, guard)
+    if g not in (0, 1, 2, 3):
+        raise ValueError(f"guard: one of {list(DVB_T_GUARDS)}")
+    return int(g)
+
+
+def _dvbt_v(v) -> int:
+    if v not in (2, 4, 6):
+        raise ValueError("v: 2, 4 or 6 bits per carrier")
+    return int(v)
+
+
+def wk_prbs(n) -> np.ndarray:
+    """wk_prbs (dvb_t.rs:390-402): the first n <= 1705 bits of the X^11 + X^2 + 1 reference sequence."""
+    if not 0 <= int(n) <= DVB_T_ACTIVE_CARRIERS:
+        raise ValueError("wk_prbs: at most 1705 bits (one per active carrier)")
+    return _dvbt_constants()[4][:int(n)].copy()
+
+
+def boosted_pilot_value(wk) -> np.complex64:
+    """boosted_pilot_value (dvb_t.rs:408-410): (4/3) 2 (1/2 - w_k), imaginary part 0."""
+    return np.complex64(_L.orion_dvbt_boosted_pilot_value(int(wk) & 0xff))
+
+
+def dvb_t_cp_len_2k(guard) -> int:
+    """GuardInterval::cp_len_2k: 64, 128, 256, 512."""
+    return DVB_T_N_FFT >> (5 - _dvbt_guard(guard))
+
+
+def scattered_pilot_indices(phase) -> np.ndarray:
+    """scattered_pilot_indices (dvb_t.rs:439-444): the active carriers k = 3 (phase mod 4) + 12 p <= 1704."""
+    return np.arange(3 * (int(phase) % 4), DVB_T_KMAX + 1, 12, dtype=np.int64)
+
+
+def tps_carrier_bins() -> np.ndarray:
+    return _dvbt_constants()[3].astype(np.int64)
+
+
+def continual_pilot_bins() -> np.ndarray:
+    return _dvbt_constants()[2].astype(np.int64)
+
+
+DVB_T_CONTINUAL_PILOTS_2K = tuple(int(v) for v in _dvbt_constants()[0])
+DVB_T_TPS_CARRIERS_2K = tuple(int(v) for v in _dvbt_constants()[1])
+
+
+def dvb_t_2k_plans(guard) -> list:
+    """dvb_t_2k_plans (dvb_t.rs:494-521) with ScatteredGridCycle's reference pilots (:559-569): a dict
+    per phase: cp_len, data_bins (1512, active-carrier order), pilot_bins / pilot_values (every
+    reserved carrier: continual, the phase's scattered, TPS, with its boosted value), ref_bins /
+    ref_values (the channel references: the pilots minus the 17 TPS bins, sorted by transform
+    bin) and role (2048: >= 0 the data index, -1 null, -2 / -3 a pilot + / -, -4 - j TPS carrier
+    j). The library refuses to build its tables unless each phase has exactly 1512 data carriers."""
+    cp, out = dvb_t_cp_len_2k(guard), []
+    for p in range(4):
+        db, pb, pv = np.zeros(1512, np.uint32), np.zeros(256, np.uint32), np.zeros(256, np.float32)
+        rb, rv, role = np.zeros(256, np.uint32), np.zeros(256, np.float32), np.zeros(2048, np.int32)
+        npil, nref = C.c_size_t(0), C.c_size_t(0)
+        _arg_check(_L.orion_dvbt_phase(p, db.ctypes.data, pb.ctypes.data, pv.ctypes.data, C.byref(npil), rb.ctypes.data,
+                                       rv.ctypes.data, C.byref(nref), role.ctypes.data))
+        out.append({"cp_len": cp, "data_bins": db.astype(np.int64), "pilot_bins": pb[:npil.value].astype(np.int64),
+                    "pilot_values": pv[:npil.value].astype(np.complex64), "ref_bins": rb[:nref.value].astype(np.int64),
+                    "ref_values": rv[:nref.value].astype(np.complex64), "role": role})
+    return out
+
+
+def dvb_t_map_symbol(bits):
+    """dvb_t_map_symbol (dvb_t.rs:157-182): v = 2, 4 or 6 bits, or (n, v) rows -> complex64; even
+    bits on I, odd on Q, Figure 9a's Gray labels. None for another v, as the reference."""
+    b = np.ascontiguousarray(bits, np.uint8)
+    if b.shape[-1] not in (2, 4, 6) or b.ndim not in (1, 2):
+        return None
+    rows = b.reshape(-1, b.shape[-1])
+    out = np.zeros(rows.shape[0], np.complex64)
+    _arg_check(_L.orion_dvbt_map_host(rows.ctypes.data, rows.shape[0], rows.shape[1], out.ctypes.data))
+    return out[0] if b.ndim == 1 else out
+
+
+def _dvbt_syms(sym):
+    one = np.ndim(sym) == 0
+    return np.ascontiguousarray(sym, np.complex64).reshape(-1), one
+
+
+def dvb_t_demap_symbol(sym, v):
+    """dvb_t_demap_symbol (dvb_t.rs:187-216): the nearest point's bits, (v,) or (n, v) uint8."""
+    if v not in (2, 4, 6):
+        return None
+    s, one = _dvbt_syms(sym)
+    out = np.zeros((s.size, v), np.uint8)
+    _arg_check(_L.orion_dvbt_demap_host(s.ctypes.data, s.size, v, out.ctypes.data))
+    return out[0] if one else out
+
+
+def dvb_t_soft_llr(sym, v):
+    """dvb_t_soft_llr (dvb_t.rs:228-266): max-log LLRs in y0 .. y(v-1) order, positive = 0."""
+    if v not in (2, 4, 6):
+        return None
+    s, one = _dvbt_syms(sym)
+    out = np.zeros((s.size, v), np.float32)
+    _arg_check(_L.orion_dvbt_llr_host(s.ctypes.data, s.size, v, out.ctypes.data))
+    return out[0] if one else out
+
+
+def _dvbt_bits(x, n, what):
+    b = np.ascontiguousarray(x, np.uint8)
+    if b.shape != (n,):
+        raise ValueError(f"{what}: {n} bits, one per element")
+    return b
+
+
+def tps_bch_encode(info) -> np.ndarray:
+    """tps_bch_encode (dvb_t_tps.rs:109-118): 53 bits -> [info | 14 parity bits], generator 0x4377."""
+    b, out = _dvbt_bits(info, TPS_INFO_BITS, "info"), np.zeros(TPS_CODEWORD_BITS, np.uint8)
+    _check(_L.orion_dvbt_tps_bch_encode(b.ctypes.data, out.ctypes.data))
+    return out
+
+
+def tps_bch_decode(codeword):
+    """tps_bch_decode (dvb_t_tps.rs:154-247): up to two errors corrected over GF(2^7) (0x89), the
+    corrected word re-encoded as a check; the 53 information bits, or None."""
+    b = np.ascontiguousarray(codeword, np.uint8)
+    if b.shape != (TPS_CODEWORD_BITS,):
+        return None
+    out, ok = np.zeros(TPS_INFO_BITS, np.uint8), C.c_int(0)
+    _check(_L.orion_dvbt_tps_bch_decode(b.ctypes.data, out.ctypes.data, C.byref(ok)))
+    return out if ok.value else None
+
+
+class TpsWord:
+    """TpsWord (dvb_t_tps.rs:293-450): frame_number 0..3, constellation "qpsk" / "qam16" / "qam64",
+    code_rate_hp "1/2" .. "7/8", guard "1/32" .. "1/4", cell_id one byte."""
+
+    def __init__(self, frame_number, constellation, code_rate_hp, guard, cell_id):
+        if constellation not in _DVBT_ORDERS:
+            raise ValueError(f"constellation: one of {list(_DVBT_ORDERS)}")
+        self.frame_number, self.constellation, self.code_rate_hp = int(frame_number), constellation, code_rate_hp
+        self.guard, self.cell_id = {v: k for k, v in DVB_T_GUARDS.items()}[_dvbt_guard(guard)], int(cell_id)
+        _fec_rate(code_rate_hp)
+
+    def _fields(self):
+        return np.array([self.frame_number & 3, _DVBT_ORDERS[self.constellation], _fec_rate(self.code_rate_hp),
+                         DVB_T_GUARDS[self.guard], self.cell_id & 0xff], np.int32)
+
+    @classmethod
+    def _from_fields(cls, f):
+        return cls(int(f[0]), {v: k for k, v in _DVBT_ORDERS.items()}[int(f[1])],
+                   {v: k for k, v in FEC_RATES.items()}[int(f[2])], int(f[3]), int(f[4]))
+
+    def pack(self) -> np.ndarray:
+        """The 68 bits s0 .. s67: s0 = 0, the sync word by frame parity, the fields, the BCH parity."""
+        f, out = self._fields(), np.zeros(68, np.uint8)
+        _arg_check(_L.orion_dvbt_tps_pack(f.ctypes.data, out.ctypes.data))
+        return out
+
+    @classmethod
+    def unpack(cls, bits):
+        """unpack (dvb_t_tps.rs:425-449): None for an uncorrectable word or a reserved constellation
+        or rate code; s0 is ignored."""
+        b = np.ascontiguousarray(bits, np.uint8)
+        if b.shape != (68,):
+            return None
+        f, ok = np.zeros(5, np.int32), C.c_int(0)
+        _check(_L.orion_dvbt_tps_unpack(b.ctypes.data, f.ctypes.data, C.byref(ok)))
+        return cls._from_fields(f) if ok.value else None
+
+    def astuple(self):
+        return (self.frame_number, self.constellation, self.code_rate_hp, self.guard, self.cell_id)
+
+    def __eq__(self, o):
+        return isinstance(o, TpsWord) and self.astuple() == o.astuple()
+
+    def __hash__(self):
+        return hash(self.astuple())
+
+    def __repr__(self):
+        return "TpsWord(frame_number=%d, constellation=%r, code_rate_hp=%r, guard=%r, cell_id=%d)" % self.astuple()
+
+
+class TpsEncoder:
+    """TpsEncoder (dvb_t_tps.rs:491-538): DBPSK along the symbol axis from the w_k reference signs."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._sign, self.symbol = np.float32(1.0), 0
+
+    def next_symbol(self, bit) -> np.ndarray:
+        if self.symbol > 0 and (int(bit) & 1):
+            self._sign = -self._sign
+        self.symbol += 1
+        return (self._sign * _tps_reference_signs()).astype(np.complex64)
+
+
+def _tps_reference_signs() -> np.ndarray:
+    one = np.zeros(68, np.uint8)
+    out = np.zeros(17, np.complex64)
+    _check(_L.orion_dvbt_tps_encode_host(one.ctypes.data, 1, out.ctypes.data))
+    return out.real.astype(np.float32)
+
+
+class TpsDecoder:
+    """TpsDecoder (dvb_t_tps.rs:546-614): bit l = (the 17 products cell conj(prev), real parts summed
+    in carrier order) < 0, so a sum of exactly 0 gives 0; bit 0 is 0."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._cells = []
+
+    def feed_symbol(self, cells):
+        c = np.ascontiguousarray(cells, np.complex64)
+        if c.ndim != 1 or c.size < 17:
+            raise ValueError("cells: the 17 TPS cells of one symbol")
+        self._cells.append(c[:17].copy())
+
+    def bits(self) -> np.ndarray:
+        if not self._cells:
+            return np.zeros(0, np.uint8)
+        c = np.ascontiguousarray(np.stack(self._cells), np.complex64)
+        out, n = np.zeros(68, np.uint8), C.c_size_t(0)
+        _check(_L.orion_dvbt_tps_decide_host(c.ctypes.data, c.shape[0], out.ctypes.data, C.byref(n)))
+        return out[:n.value]
+
+    def is_complete(self) -> bool:
+        return len(self._cells) >= 68
+
+    def word(self):
+        return TpsWord.unpack(self.bits()[:68]) if self.is_complete() else None
+
+
+class GiSyncConfig:
+    """GiSyncConfig (dvb_t_gi_sync.rs:57-127): rho weights the energy term of |gamma| - rho Phi,
+    max_symbols bounds the coherent accumulation, origin_score_ratio guards the origin unwrap."""
+
+    def __init__(self, rho=0.95, max_symbols=4, origin_score_ratio=0.5):
+        self.rho, self.max_symbols, self.origin_score_ratio = float(rho), int(max_symbols), float(origin_score_ratio)
+        if self.max_symbols < 0:
+            raise ValueError("max_symbols is not negative")
+
+
+class GiSyncResult:
+    """GiSyncResult (dvb_t_gi_sync.rs:132-143) with the winning offset's sums: start_sample, cfo_hz,
+    score, gamma (complex64) and phi (float32)."""
+
+    def __init__(self, start_sample, cfo_hz, score, gamma=0j, phi=0.0):
+        self.start_sample, self.cfo_hz, self.score = int(start_sample), np.float32(cfo_hz), np.float32(score)
+        self.gamma, self.phi = np.complex64(gamma), np.float32(phi)
+
+    def __repr__(self):
+        return f"GiSyncResult(start_sample={self.start_sample}, cfo_hz={self.cfo_hz}, score={self.score})"
+
+
+def _gi_sync_host(iq, n_fft, cp_len, fs, search_len, cfg, metric=False):
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    cfg = cfg if cfg is not None else GiSyncConfig()
+    if min(int(n_fft), int(cp_len), int(search_len)) < 0:
+        raise ValueError("n_fft, cp_len and search_len are not negative")
+    start, found, out = C.c_int64(0), C.c_int(0), np.zeros(5, np.float32)
+    m = np.zeros(int(search_len), np.float32) if metric else None
+    _arg_check(_L.orion_dvbt_gi_sync_host(iq.ctypes.data, iq.size, int(n_fft), int(cp_len), float(fs), int(search_len),
+                                          cfg.rho, cfg.max_symbols, cfg.origin_score_ratio, C.byref(start),
+                                          out.ctypes.data, C.byref(found), m.ctypes.data if metric else None))
+    res = GiSyncResult(start.value, out[0], out[1], complex(out[2], out[3]), out[4]) if found.value else None
+    return (res, m if found.value else None) if metric else res
+
+
+def dvb_t_gi_sync_with(iq, n_fft, cp_len, fs, search_len, cfg=None):
+    """dvb_t_gi_sync_with (dvb_t_gi_sync.rs:169-286) on the host: gamma and Phi summed sequentially
+    over k, then over up to max_symbols symbols that fit, Phi halved after the sum; the metric
+    |gamma| - rho Phi; the argmax by total_cmp with the last of equal maxima; the two-condition
+    origin unwrap on single-symbol scores; score = min(|gamma| / Phi, 1); cfo_hz = -atan2(gamma.im,
+    gamma.re) fs / (TAU n_fft). |gamma| is the float32 rounding of the float64 square root of the
+    float64 sum of the two exact squares. None where the reference returns None."""
+    return _gi_sync_host(iq, n_fft, cp_len, fs, search_len, cfg)
+
+
+def dvb_t_gi_sync(iq, n_fft, cp_len, fs, search_len):
+    return _gi_sync_host(iq, n_fft, cp_len, fs, search_len, None)
+
+
+def dvb_t_gi_metric(iq, n_fft, cp_len, fs, search_len, cfg=None):
+    """(result, metric float32 (search_len,)) of dvb_t_gi_sync_with: the ranked metric per offset."""
+    return _gi_sync_host(iq, n_fft, cp_len, fs, search_len, cfg, metric=True)
+
+
+def dvb_t_gi_refine(iq, n_fft, cp_len, fs, coarse, radius, cfg=None):
+    """dvb_t_gi_refine_with (dvb_t_gi_sync.rs:319-338): a plain argmax within coarse +- radius."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    cfg = cfg if cfg is not None else GiSyncConfig()
+    start = max(int(coarse) - int(radius), 0)
+    if start > iq.size:
+        return None
+    sub = np.ascontiguousarray(iq[start:])
+    r = _gi_sync_host(sub, n_fft, cp_len, fs, min(2 * int(radius) + 1, sub.size), GiSyncConfig(cfg.rho, cfg.max_symbols, 0.0))
+    if r is not None:
+        r.start_sample += start
+    return r
+
+
+def dvb_t_integer_cfo(freq, n_fft, max_bins):
+    """dvb_t_integer_cfo (dvb_t_gi_sync.rs:380-417): (bins, confidence) of the shift in -max_bins ..
+    max_bins with the most energy at the 45 continual-pilot bins (the first of equal maxima), or None."""
+    fq = _ofdm_arr(freq, np.complex64, "freq")
+    bins, conf, found = C.c_int32(0), C.c_float(0.0), C.c_int(0)
+    _arg_check(_L.orion_dvbt_integer_cfo_host(fq.ctypes.data, fq.size, int(n_fft), int(max_bins), C.byref(bins),
+                                              C.byref(conf), C.byref(found)))
+    return (int(bins.value), np.float32(conf.value)) if found.value else None
+
+
+def dvb_t_mod_symbols(coded_bits, v, cp_len, tps_bits, n_symbols, roll_off=0) -> np.ndarray:
+    """The frame modulator from the coded bits on (modulate/dvb_t_frame.rs:213-261), host: Figure-9a
+    mapping through the four-phase grid, the TPS cells, inverse transform, cyclic prefix, window.
+    A data carrier whose v bits lie past the coded bits is zero."""
+    b = np.ascontiguousarray(coded_bits, np.uint8).reshape(-1)
+    t = _dvbt_bits(tps_bits, 68, "tps_bits")
+    out = np.zeros(int(n_symbols) * (DVB_T_N_FFT + int(cp_len)), np.complex64)
+    _arg_check(_L.orion_dvbt_mod_symbols_host(b.ctypes.data, b.size, _dvbt_v(v), int(cp_len), t.ctypes.data, int(n_symbols),
+                                              int(roll_off), out.ctypes.data))
+    return out
+
+
+def dvb_t_demod_symbols(iq, n_symbols, cp_len, backoff, v, syms=False):
+    """The frame demodulator's symbol loop (demodulate/dvb_t_frame.rs:497-583) from an acquired
+    start, host: (llr float32 (n_symbols, 1512 v), cells complex64 (n_symbols, 17)[, equalized
+    data symbols complex64 (n_symbols, 1512)])."""
+    iq = _ofdm_arr(iq, np.complex64, "iq")
+    ns, sps = int(n_symbols), DVB_T_N_FFT + int(cp_len)
+    if iq.size < ns * sps:
+        raise ValueError("iq: n_symbols whole symbols")
+    llr, cells = np.zeros((ns, 1512 * _dvbt_v(v)), np.float32), np.zeros((ns, 17), np.complex64)
+    eq = np.zeros((ns, 1512), np.complex64) if syms else None
+    _arg_check(_L.orion_dvbt_demod_symbols_host(iq.ctypes.data, ns, int(cp_len), int(backoff), v, llr.ctypes.data,
+                                                cells.ctypes.data, eq.ctypes.data if syms else None))
+    return (llr, cells, eq) if syms else (llr, cells)
+
+
+def _dvbt_cuda(x, dtype, dims, what):
+    import torch
+
+    if not _is_torch(x) or not x.is_cuda or not x.is_contiguous() or x.dtype != getattr(torch, dtype) or x.dim() != dims:
+        raise ValueError(f"{what}: a contiguous {dims}-D {dtype} CUDA tensor")
+    return x
+
+
+def _dvbt_numpy_in(x, dtype, what):
+    import torch
+
+    if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 2:
+        raise ValueError(f"{what}: expected a 2-D {np.dtype(dtype).name} array")
+    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+
+
+def _dvbt_tps_words(tps_bits, frames, device):
+    """(frames, 68) bits -> (frames, 3) int32 on the device, bit l of a row's 96 the bit s_l."""
+    import torch
+
+    t = np.ascontiguousarray(tps_bits, np.uint8)
+    if t.shape != (frames, 68):
+        raise ValueError("tps_bits: (frames, 68) bits")
+    padded = np.zeros((frames, 96), np.uint8)
+    padded[:, :68] = t & 1
+    words = np.packbits(padded, axis=1, bitorder="little").view(np.uint32).reshape(frames, 3)
+    return torch.from_numpy(words.view(np.int32).copy()).to(device)
+
+
+def dvb_t_mod_symbols_batch(coded_bits, v, cp_len, tps_bits, n_symbols, roll_off=0, nbits=None, stream=None):
+    """dvb_t_mod_symbols for every row of coded_bits uint8 (frames, row_bits) on the GPU, one
+    workgroup per (frame, symbol): tps_bits (frames, 68) host bits (every frame its own word),
+    nbits (frames,) the bits a row really holds (default row_bits) -> complex64 (frames, n_symbols
+    (2048 + cp_len)), row k the host's bits. numpy in -> numpy out; a contiguous torch CUDA tensor
+    stays resident, queued on torch's current stream or on stream."""
+    import torch
+
+    if not _is_torch(coded_bits):
+        out = dvb_t_mod_symbols_batch(_dvbt_numpy_in(coded_bits, np.uint8, "coded_bits"), v, cp_len, tps_bits, n_symbols,
+                                      roll_off, nbits, stream)
+        if stream is not None:
+            torch.cuda.synchronize()
+        return out.cpu().numpy()
+    b = _dvbt_cuda(coded_bits, "uint8", 2, "coded_bits")
+    frames, row_bits, ns = int(b.shape[0]), int(b.shape[1]), int(n_symbols)
+    with _TorchOn(b, stream):
+        words = _dvbt_tps_words(tps_bits, frames, b.device)
+        nb = None
+        if nbits is not None:
+            nb = np.ascontiguousarray(nbits, np.int64)
+            if nb.shape != (frames,) or nb.min(initial=0) < 0 or nb.max(initial=0) > row_bits:
+                raise ValueError("nbits: (frames,) counts within a row")
+            nb = torch.from_numpy(nb.astype(np.int32)).to(b.device)
+        out = torch.zeros((frames, ns * (DVB_T_N_FFT + int(cp_len))), dtype=torch.complex64, device=b.device)
+        _arg_check(_L.orion_dvbt_mod_symbols_device(b.data_ptr(), frames, row_bits, nb.data_ptr() if nb is not None else None,
+                                                    words.data_ptr(), _dvbt_v(v), int(cp_len), ns, int(roll_off),
+                                                    out.data_ptr(), SyncEngine._stream(b, stream)))
+    return out
+
+
+_GI_BATCH_KEYS = (("start", "int32", 1), ("found", "int32", 1), ("score", "float32", 1), ("cfo_hz", "float32", 1),
+                  ("gamma", "complex64", 1), ("phi", "float32", 1), ("metric", "float32", None),
+                  ("gamma_all", "complex64", None), ("phi_all", "float32", None))
+
+
+def dvb_t_gi_sync_batch(iq, n_fft, cp_len, fs, search_len, cfg=None, stream=None) -> dict:
+    """dvb_t_gi_sync_with for every row of iq (ncap, n) on the GPU, one independent search per
+    capture. Returns per capture start int32, found int32 (0 where the host returns None: the
+    capture is too short), score, cfo_hz, phi float32 and gamma complex64, and per offset metric,
+    phi_all float32 and gamma_all complex64 (ncap, search_len). Everything but cfo_hz carries the
+    host's bits; cfo_hz is the device's atan2f. numpy in -> numpy out; a contiguous
+    2-D complex64 CUDA tensor stays resident, queued on torch's current stream or on stream."""
+    import torch
+
+    if not _is_torch(iq):
+        out = dvb_t_gi_sync_batch(_dvbt_numpy_in(iq, np.complex64, "iq"), n_fft, cp_len, fs, search_len, cfg, stream)
+        if stream is not None:
+            torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+    iq = _dvbt_cuda(iq, "complex64", 2, "iq")
+    cfg = cfg if cfg is not None else GiSyncConfig()
+    ncap, n, sl = int(iq.shape[0]), int(iq.shape[1]), int(search_len)
+    if min(int(n_fft), int(cp_len), sl) < 0:
+        raise ValueError("n_fft, cp_len and search_len are not negative")
+    with _TorchOn(iq, stream):
+        out = {}
+        for k, dt, w in _GI_BATCH_KEYS:
+            out[k] = torch.zeros((ncap,) if w == 1 else (ncap, max(sl, 1)), dtype=getattr(torch, dt), device=iq.device)
+        if ncap:
+            oc = _GiOutC(*[out[k].data_ptr() for k, _, _ in _GI_BATCH_KEYS])
+            _arg_check(_L.orion_dvbt_gi_sync_batch_device(iq.data_ptr(), ncap, n, int(n_fft), int(cp_len), float(fs), sl,
+                                                          cfg.rho, cfg.max_symbols, cfg.origin_score_ratio, C.byref(oc),
+                                                          SyncEngine._stream(iq, stream)))
+        for k in ("metric", "gamma_all", "phi_all"):
+            out[k] = out[k][:, :sl]
+    return out
+
+
+def dvb_t_demod_symbols_batch(iq, start, found, n_symbols, cp_len, backoff, v, syms=False, stream=None) -> dict:
+    """dvb_t_demod_symbols for every row of iq (ncap, n) on the GPU from start[c] (int32 (ncap,), as
+    dvb_t_gi_sync_batch gives it): llr float32 (ncap, n_symbols, 1512 v), cells complex64 (ncap,
+    n_symbols, 17) and with syms the equalized data symbols (ncap, n_symbols, 1512), each the
+    host's bits; zeros for a capture with found[c] == 0 or whose n_symbols symbols do not fit."""
+    import torch
+
+    if not _is_torch(iq):
+        dev = _dvbt_numpy_in(iq, np.complex64, "iq")
+        st = torch.from_numpy(np.ascontiguousarray(start, np.int32)).to(dev.device)
+        fd = torch.from_numpy(np.ascontiguousarray(found, np.int32)).to(dev.device)
+        out = dvb_t_demod_symbols_batch(dev, st, fd, n_symbols, cp_len, backoff, v, syms, stream)
+        if stream is not None:
+            torch.cuda.synchronize()
+        return {k: x.cpu().numpy() for k, x in out.items()}
+    iq = _dvbt_cuda(iq, "complex64", 2, "iq")
+    ncap, n, ns = int(iq.shape[0]), int(iq.shape[1]), int(n_symbols)
+    st, fd = _dvbt_cuda(start, "int32", 1, "start"), _dvbt_cuda(found, "int32", 1, "found")
+    if int(st.shape[0]) != ncap or int(fd.shape[0]) != ncap or int(backoff) < 0:
+        raise ValueError("start, found: one entry per capture; backoff is not negative")
+    with _TorchOn(iq, stream):
+        out = {"llr": torch.zeros((ncap, ns, 1512 * _dvbt_v(v)), dtype=torch.float32, device=iq.device),
+               "cells": torch.zeros((ncap, ns, 17), dtype=torch.complex64, device=iq.device)}
+        if syms:
+            out["syms"] = torch.zeros((ncap, ns, 1512), dtype=torch.complex64, device=iq.device)
+        _arg_check(_L.orion_dvbt_demod_symbols_device(iq.data_ptr(), ncap, n, st.data_ptr(), fd.data_ptr(), ns, int(cp_len),
+                                                      int(backoff), v, out["llr"].data_ptr(), out["cells"].data_ptr(),
+                                                      out["syms"].data_ptr() if syms else None,
+                                                      SyncEngine._stream(iq, stream)))
+    return out
+
+
+def dvb_t_tps_decode_batch(cells, stream=None) -> dict:
+    """TpsDecoder + TpsWord::unpack over the first 68 symbols of cells complex64 (frames, n_symbols,
+    17) on the GPU, one wave per frame: fields int32 (frames, 5) (frame_number, constellation,
+    code rate, guard, cell_id as the library's codes) and status int32 (frames,): 0 decoded, 1 not
+    (fewer than 68 symbols, an uncorrectable word, a reserved code)."""
+    import torch
+
+    if not _is_torch(cells):
+        c = np.ascontiguousarray(cells, np.complex64)
+        if c.ndim != 3 or c.shape[2] != 17:
+            raise ValueError("cells: (frames, n_symbols, 17) complex64")
+        out = dvb_t_tps_decode_batch(torch.from_numpy(c).cuda(), stream)
+        if stream is not None:
+            torch.cuda.synchronize()
+        return {k: x.cpu().numpy() for k, x in out.items()}
+    c = _dvbt_cuda(cells, "complex64", 3, "cells")
+    if int(c.shape[2]) != 17:
+        raise ValueError("cells: (frames, n_symbols, 17) complex64")
+    frames = int(c.shape[0])
+    with _TorchOn(c, stream):
+        out = {"fields": torch.zeros((frames, 5), dtype=torch.int32, device=c.device),
+               "status": torch.ones((frames,), dtype=torch.int32, device=c.device)}
+        _arg_check(_L.orion_dvbt_tps_decode_device(c.data_ptr(), frames, int(c.shape[1]), out["fields"].data_ptr(),
+                                                   out["status"].data_ptr(), SyncEngine._stream(c, stream)))
+    return out
+
+
+def _dvbt_fs() -> float:
+    """dvb_t_fs_for_bandwidth(1 MHz) (dvb_t.rs:726-728), the frame classes' sample rate."""
+    return float(np.float32(1_000_000.0) * np.float32(DVB_T_N_FFT) / np.float32(DVB_T_ACTIVE_CARRIERS))
+
+
+class DvbTFrameParams:
+    """DvbTFrameParams (dvb_t.rs:898-953): guard "1/32" .. "1/4", constellation "qpsk" / "qam16" /
+    "qam64", code_rate "1/2" .. "7/8", frame_number 0..3 and the cell-id byte."""
+
+    def __init__(self, guard="1/32", constellation="qpsk", code_rate="1/2", frame_number=0, cell_id=0):
+        self._tps = TpsWord(frame_number, constellation, code_rate, guard, cell_id)
+        if not 0 <= int(frame_number) <= 3 or not 0 <= int(cell_id) <= 255:
+            raise ValueError("frame_number 0..3, cell_id 0..255")
+        self.guard, self.constellation, self.code_rate = self._tps.guard, constellation, code_rate
+        self.frame_number, self.cell_id = int(frame_number), int(cell_id)
+        self.cp_len, self.bits_per_carrier = dvb_t_cp_len_2k(guard), 2 * _DVBT_ORDERS[constellation]
+        self.fs = _dvbt_fs()
+
+    def tps_word(self) -> TpsWord:
+        return self._tps
+
+    def scheme(self) -> FrameScheme:
+        """The DVB coding chain: no CRC, RS(204,188), the K = 7 code at the frame's rate, Forney
+        I = 12 / M = 17, no scrambler (the TS energy dispersal runs outside the chain)."""
+        return FrameScheme(crc="none", outer=("rs", 204, 16), inner=("conv", self.code_rate, "dvb_k7"),
+                           outer_interleaver=("forney", 12, 17), scrambler=None)
+
+    def with_frame(self, frame_number, cell_id) -> "DvbTFrameParams":
+        return DvbTFrameParams(self.guard, self.constellation, self.code_rate, frame_number, cell_id)
+
+
+class DvbTFrame:
+    """DvbTFrame (modulate/dvb_t_frame.rs:47-55)."""
+
+    def __init__(self, iq, n_symbols, samples_per_symbol):
+        self.iq, self.n_symbols, self.samples_per_symbol = iq, int(n_symbols), int(samples_per_symbol)
+
+
+class DvbTFrameMod:
+    """DvbTFrameMod (modulate/dvb_t_frame.rs:61-277): a TS payload -> one preamble-less DVB-T frame.
+    modulate is the library's host code; modulate_frames the same frames batched on the GPU."""
+
+    def __init__(self, params):
+        if not isinstance(params, DvbTFrameParams):
+            raise ValueError("params: a DvbTFrameParams")
+        self.params, self._roll, self._lowpass = params, 0, None
+
+    def with_symbol_window(self, roll_off) -> "DvbTFrameMod":
+        if int(roll_off) < 0 or int(roll_off) > 4095:
+            raise ValueError("roll_off: 0 .. 4095 samples")
+        self._roll = int(roll_off)
+        return self
+
+    def with_tx_lowpass(self, lowpass) -> "DvbTFrameMod":
+        if not isinstance(lowpass, TxLowpass):
+            raise ValueError("lowpass: a TxLowpass")
+        self._lowpass = lowpass
+        return self
+
+    @staticmethod
+    def tx_lowpass_for_2k(num_taps, stopband_db) -> TxLowpass:
+        return TxLowpass.for_null_band(DVB_T_N_FFT, DVB_T_KMAX // 2, int(num_taps), float(stopband_db))
+
+    def plan(self, payload_len):
+        """(n_symbols, target_packets): max(payload symbols, 68), and the packets after null-packet
+        stuffing, the fewest (at least the payload's) whose coded stream fills every carrier."""
+        p, sch = self.params, self.params.scheme()
+        per_sym = DVB_T_DATA_CARRIERS * p.bits_per_carrier
+        n_real = max(1, -(-int(payload_len) // 187))
+        n_symbols = max(symbols_for_coded_bits(DVB_T_DATA_CARRIERS, p.bits_per_carrier,
+                                               block_plan(n_real * TS_PACKET_LEN, sch).coded_bits), TPS_SYMBOLS_PER_FRAME)
+        target = n_real
+        while block_plan(target * TS_PACKET_LEN, sch).coded_bits < n_symbols * per_sym:
+            target += 1
+        return n_symbols, target
+
+    def _ts(self, payload, target) -> np.ndarray:
+        return ts_energy_disperse(ts_stuff_null_packets(ts_packetize(payload), target))
+
+    def modulate(self, payload) -> DvbTFrame:
+        """modulate (modulate/dvb_t_frame.rs:147-276) on the host."""
+        payload = _bytes_arg(payload, "payload")
+        p = self.params
+        n_symbols, target = self.plan(payload.size)
+        coded = encode_chain(self._ts(payload, target), p.scheme(), 0)
+        iq = dvb_t_mod_symbols(coded, p.bits_per_carrier, p.cp_len, p.tps_word().pack(), n_symbols, self._roll)
+        if self._lowpass is not None:
+            iq = self._lowpass.apply(iq)
+        return DvbTFrame(iq, n_symbols, DVB_T_N_FFT + p.cp_len)
+
+    def modulate_frames(self, payloads, frame_numbers=None, cell_ids=None, stream=None):
+        """A batch of equal-length payloads on the GPU: uint8 (B, n) -> complex64 (B, n_symbols (2048
+        + cp_len)), row k equal to modulate of payload k under frame_numbers[k] / cell_ids[k]
+        (default: the parameters'). The TS adaptation (packets, null-packet stuffing, energy
+        dispersal) runs on the host; then frame_encode_chain_batch and k_dvbt_mod. numpy in ->
+        numpy out; a contiguous torch CUDA tensor stays resident, queued on torch's current stream
+        or on stream. with_tx_lowpass is the host path's: ValueError here."""
+        import torch
+
+        if self._lowpass is not None:
+            raise ValueError("modulate_frames: with_tx_lowpass is taken by modulate (the host path) only")
+        if not _is_torch(payloads):
+            p, _ = _fec2_arg(payloads, "payloads", "uint8", (2,))
+            out = self.modulate_frames(torch.from_numpy(p).cuda(), frame_numbers, cell_ids, stream)
+            if stream is not None:
+                torch.cuda.synchronize()
+            return out.cpu().numpy()
+        pl, _ = _fec2_arg(payloads, "payloads", "uint8", (2,))
+        par = self.params
+        frames, n = int(pl.shape[0]), int(pl.shape[1])
+        fn = np.full(frames, par.frame_number) if frame_numbers is None else np.asarray(frame_numbers, np.int64)
+        ci = np.full(frames, par.cell_id) if cell_ids is None else np.asarray(cell_ids, np.int64)
+        if fn.shape != (frames,) or ci.shape != (frames,):
+            raise ValueError("frame_numbers, cell_ids: one entry per frame")
+        n_symbols, target = self.plan(n)
+        tps = np.stack([par.with_frame(int(a), int(b)).tps_word().pack() for a, b in zip(fn, ci)]) if frames else \
+            np.zeros((0, 68), np.uint8)
+        with _TorchOn(pl, stream):
+            if stream is not None:
+                torch.cuda.current_stream(pl.device).synchronize()
+            host = pl.cpu().numpy()
+            ts = np.stack([self._ts(row, target) for row in host]) if frames else np.zeros((0, target * 188), np.uint8)
+            coded = frame_encode_chain_batch(torch.from_numpy(ts).to(pl.device), par.scheme(), stream=stream)
+            return dvb_t_mod_symbols_batch(coded, par.bits_per_carrier, par.cp_len, tps, n_symbols, self._roll,
+                                           stream=stream)
+
+
+class DvbTRxError(Exception):
+    """DvbTRxError (demodulate/dvb_t_frame.rs:213-222): kind "acquisition", "incomplete",
+    "tps_decode" or "payload_decode"; code its DVB_T_RX_ERRORS number."""
+
+    def __init__(self, kind):
+        if kind not in DVB_T_RX_ERRORS:
+            kind = {v: k for k, v in DVB_T_RX_ERRORS.items()}[int(kind)]
+        super().__init__(kind)
+        self.kind, self.code = kind, DVB_T_RX_ERRORS[kind]
+
+    def __eq__(self, o):
+        return (isinstance(o, DvbTRxError) and o.kind == self.kind) or o == self.kind
+
+    def __hash__(self):
+        return hash(self.kind)
+
+
+class DvbTRxFrame:
+    """DvbTRxFrame (demodulate/dvb_t_frame.rs:201-209): payload, tps (a TpsWord) and diagnostics, a
+    dict with cfo_hz (total), sync_score, timing_offset_samples, integer_cfo_bins, outer_fec_ok,
+    rs_corrected_bytes, and evm_db / channel_ber / inner_ber, which stay None."""
+
+    def __init__(self, payload, tps, diagnostics):
+        self.payload, self.tps, self.diagnostics = payload, tps, diagnostics
+
+
+class DvbTFrameDemod:
+    """DvbTFrameDemod (demodulate/dvb_t_frame.rs:239-768): IQ at an unknown start -> payload, TPS word
+    and diagnostics. decode is the library's host code and raises DvbTRxError; decode_frames
+    decodes a batch of captures on the GPU and reports the same outcome per capture."""
+
+    def __init__(self, params):
+        if not isinstance(params, DvbTFrameParams):
+            raise ValueError("params: a DvbTFrameParams")
+        self.params, self._icfo, self._backoff = params, False, 0
+
+    def with_integer_cfo_correction(self, on=True) -> "DvbTFrameDemod":
+        self._icfo = bool(on)
+        return self
+
+    def with_rx_window_backoff(self, backoff) -> "DvbTFrameDemod":
+        if int(backoff) < 0:
+            raise ValueError("backoff is not negative")
+        self._backoff = int(backoff)
+        return self
+
+    def integer_cfo_correct(self, iq):
+        """integer_cfo_correct (demodulate/dvb_t_frame.rs:342-394): (the rotated buffer or None, the
+        estimate in bins or None); eight symbols' |X|^2 accumulated at the CP boundary, +-32 bins."""
+        p = self.params
+        sps = DVB_T_N_FFT + p.cp_len
+        acq = dvb_t_gi_sync(iq, DVB_T_N_FFT, p.cp_len, p.fs, sps)
+        if acq is None:
+            return None, None
+        accum = np.zeros(DVB_T_N_FFT, np.complex64)
+        for s in range(INTEGER_CFO_ACCUM_SYMBOLS):
+            off = acq.start_sample + s * sps
+            if off + sps > iq.size:
+                break
+            f = fft_host(np.ascontiguousarray(iq[off + p.cp_len:off + sps]), DVB_T_N_FFT)
+            e = (f.real * f.real + f.imag * f.imag).astype(np.float32)  # norm_sqr, one rounding per step
+            accum = (accum.real + e).astype(np.float32).astype(np.complex64)
+        est = dvb_t_integer_cfo(accum, DVB_T_N_FFT, INTEGER_CFO_MAX_BINS)
+        if est is None:
+            return None, None
+        k = est[0]
+        if k == 0:
+            return None, 0
+        return ofdm_rotate_block(iq, float(-np.float32(k) * np.float32(p.fs) / np.float32(DVB_T_N_FFT)), p.fs), k
+
+    def decode(self, iq, n_symbols, payload_len) -> DvbTRxFrame:
+        """decode (demodulate/dvb_t_frame.rs:406-767) on the host: TPS from the raw bins of the first
+        68 symbols; the fractional CFO reported, not corrected; the payload's own packets (the
+        prefix of the coded stream) decoded."""
+        iq = _ofdm_arr(iq, np.complex64, "iq")
+        p, n_symbols, payload_len = self.params, int(n_symbols), int(payload_len)
+        sps = DVB_T_N_FFT + p.cp_len
+        bins = None
+        if self._icfo:
+            rotated, bins = self.integer_cfo_correct(iq)
+            iq = rotated if rotated is not None else iq
+        acq = dvb_t_gi_sync(iq, DVB_T_N_FFT, p.cp_len, p.fs, sps)
+        if acq is None:
+            raise DvbTRxError("acquisition")
+        start = acq.start_sample
+        if iq.size < start + n_symbols * sps:
+            raise DvbTRxError("incomplete")
+        spacing = np.float32(p.fs) / np.float32(DVB_T_N_FFT)
+        diag = {"cfo_hz": np.float32(acq.cfo_hz + np.float32(bins or 0) * spacing), "sync_score": acq.score,
+                "timing_offset_samples": start, "integer_cfo_bins": bins, "evm_db": None, "channel_ber": None,
+                "inner_ber": None, "outer_fec_ok": None, "rs_corrected_bytes": None}
+        llr, cells = dvb_t_demod_symbols(np.ascontiguousarray(iq[start:start + n_symbols * sps]), n_symbols, p.cp_len,
+                                         self._backoff, p.bits_per_carrier)
+        dec = TpsDecoder()
+        for c in cells[:68]:
+            dec.feed_symbol(c)
+        tps = dec.word()
+        if tps is None:
+            raise DvbTRxError("tps_decode")
+        packets = max(1, -(-payload_len // 187))
+        try:
+            out = decode_chain(llr.reshape(-1), packets * TS_PACKET_LEN, p.scheme(), 0, "sum_product")
+        except (RxError, ValueError):
+            raise DvbTRxError("payload_decode") from None
+        if not out.is_valid() or out.bytes.size < packets * TS_PACKET_LEN:
+            raise DvbTRxError("payload_decode")
+        diag["outer_fec_ok"], diag["rs_corrected_bytes"] = out.outer_ok, out.outer_corrected_bytes
+        payload = ts_depacketize(ts_energy_disperse(out.bytes[:packets * TS_PACKET_LEN]))
+        if payload is None:
+            raise DvbTRxError("payload_decode")
+        return DvbTRxFrame(payload[:payload_len], tps, diag)
+
+    def decode_frames(self, iq, n_symbols, payload_len, stream=None) -> dict:
+        """decode for every row of iq complex64 (B, L) on the GPU: k_gi_metric / k_gi_select,
+        k_dvbt_demod, k_tps_decode, then frame_decode_chain_batch on each row's LLR prefix, and on
+        the host the de-dispersal and depacketizing. Returns numpy arrays per capture: error (0 or
+        the DvbTRxError code decode raises), frame_number, constellation, code_rate, guard, cell_id
+        (the TPS fields as the library's codes; 0 where no word decoded), cfo_hz, sync_score,
+        timing_offset_samples, integer_cfo_bins (-1: not measured), outer_fec_ok,
+        rs_corrected_bytes, and payloads, a list of uint8 arrays (empty where error != 0). cfo_hz is
+        the device's atan2f. with_integer_cfo_correction(True) is the host path's: ValueError."""
+        import torch
+
+        if self._icfo:
+            raise ValueError("decode_frames: with_integer_cfo_correction is taken by decode (the host path) only")
+        if not _is_torch(iq):
+            return self.decode_frames(_dvbt_numpy_in(iq, np.complex64, "iq"), n_symbols, payload_len, stream)
+        iq = _dvbt_cuda(iq, "complex64", 2, "iq")
+        p, ns, payload_len = self.params, int(n_symbols), int(payload_len)
+        B, L, sps = int(iq.shape[0]), int(iq.shape[1]), DVB_T_N_FFT + self.params.cp_len
+        E = DVB_T_RX_ERRORS
+        res = {k: np.zeros(B, np.int64) for k in ("error", "frame_number", "constellation", "code_rate", "guard", "cell_id",
+                                                  "timing_offset_samples", "rs_corrected_bytes")}
+        res.update({"cfo_hz": np.zeros(B, np.float32), "sync_score": np.zeros(B, np.float32),
+                    "integer_cfo_bins": np.full(B, -1, np.int64), "outer_fec_ok": np.zeros(B, bool),
+                    "payloads": [np.zeros(0, np.uint8) for _ in range(B)]})
+        if B == 0:
+            return res
+        packets = max(1, -(-payload_len // 187))
+        sch = p.scheme()
+        with _TorchOn(iq, stream):
+            acq = dvb_t_gi_sync_batch(iq, DVB_T_N_FFT, p.cp_len, p.fs, sps, stream=stream)
+            dem = dvb_t_demod_symbols_batch(iq, acq["start"], acq["found"], ns, p.cp_len, self._backoff, p.bits_per_carrier,
+                                            stream=stream)
+            tps = dvb_t_tps_decode_batch(dem["cells"], stream=stream)
+            need = block_plan(packets * TS_PACKET_LEN, sch).coded_bits
+            llr = dem["llr"].reshape(B, -1)
+            chain = None
+            if int(llr.shape[1]) >= need:
+                chain = frame_decode_chain_batch(llr, packets * TS_PACKET_LEN, sch, stream=stream)
+            if stream is not None:
+                torch.cuda.current_stream(iq.device).synchronize()
+            head = torch.stack([acq["start"], acq["found"], tps["status"]], dim=1).cpu().numpy()
+            fields = tps["fields"].cpu().numpy()
+            res["cfo_hz"], res["sync_score"] = acq["cfo_hz"].cpu().numpy(), acq["score"].cpu().numpy()
+            if chain is not None:
+                ok = torch.stack([chain["valid"], chain["outer_ok"]], dim=1).cpu().numpy()
+                corrected, pay = chain["corrected"].cpu().numpy(), chain["payload"].cpu().numpy()
+        found = head[:, 1] != 0
+        fits = found & (head[:, 0].astype(np.int64) + ns * sps <= L)
+        tps_ok = fits & (head[:, 2] == 0)
+        res["error"][~found] = E["acquisition"]
+        res["error"][found & ~fits] = E["incomplete"]
+        res["error"][fits & ~tps_ok] = E["tps_decode"]
+        res["timing_offset_samples"][found] = head[found, 0]
+        res["cfo_hz"][~found], res["sync_score"][~found] = 0.0, 0.0
+        for j, key in enumerate(("frame_number", "constellation", "code_rate", "guard", "cell_id")):
+            res[key][tps_ok] = fields[tps_ok, j]
+        for c in np.flatnonzero(tps_ok):
+            good = chain is not None and bool(ok[c, 0])
+            payload = ts_depacketize(ts_energy_disperse(pay[c])) if good else None
+            if payload is None:
+                res["error"][c] = E["payload_decode"]
+                continue
+            res["outer_fec_ok"][c], res["rs_corrected_bytes"][c] = bool(ok[c, 1]), int(corrected[c])
+            res["payloads"][c] = payload[:payload_len]
+        return res
